@@ -21,6 +21,14 @@ Launch (the driver's contract):
   python bench.py --gpus 1 --steps 3 --warmup 1
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step computed (its loss
+and a seeded sample of the updated parameters and Adam first moments) as
+DIR/<name>.npy, identical inputs for identical arguments, so two builds can
+be compared output for output.  --full is where secondary measurements go;
+the benchmark has none of its own today (per-op and serving figures live in
+scripts/), so the flag changes nothing yet.
 """
 
 from __future__ import annotations
@@ -57,6 +65,49 @@ def fast_random_init(module: PipelineModule, std: float, seed: int) -> None:
             m.weight.normal_(0.0, std, generator=g)
 
 
+DUMP_SAMPLE_PER_PARAM = 4096  # elements sampled from each parameter tensor
+
+
+@torch.no_grad()
+def dump_outputs(out_dir: str, module: PipelineModule, optimizer, losses,
+                 rank: int, world: int) -> None:
+    """Write what the last timed train_batch() handed its caller as .npy:
+    the returned loss (plus the loss of every timed step) and the model and
+    optimizer state it updated in place.  Those are far above the 64 MB
+    cap, so a fixed seeded sample of DUMP_SAMPLE_PER_PARAM elements per
+    tensor is written instead (same indices every run: comparable build to
+    build)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    if rank == 0:  # the loss is identical on every rank
+        np.save(os.path.join(out_dir, "loss.npy"),
+                np.asarray(losses[-1:], dtype=np.float64))
+        np.save(os.path.join(out_dir, "step_losses.npy"),
+                np.asarray(losses, dtype=np.float64))
+
+    def save_sample(name: str, tensors) -> None:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(4321)
+        chunks = []
+        for t in tensors:
+            flat = t.detach().reshape(-1)
+            n = flat.numel()
+            if n > DUMP_SAMPLE_PER_PARAM:
+                idx = torch.randint(0, n, (DUMP_SAMPLE_PER_PARAM,), generator=g)
+                flat = flat[idx.to(flat.device)]
+            chunks.append(flat.float().cpu())
+        if chunks:
+            np.save(os.path.join(out_dir, f"{prefix}{name}.npy"),
+                    torch.cat(chunks).numpy())
+
+    save_sample("params_sample", module.parameters())
+    # Adam first moment = running mean of the accumulated gradients: the
+    # part of the updated state most sensitive to the backward kernels
+    save_sample("grad_moment_sample", optimizer.exp_avg)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -85,7 +136,16 @@ def main() -> int:
     ap.add_argument("--watchdog", type=float, default=900.0,
                     help="seconds before the deadlock watchdog dumps per-rank "
                          "schedule position (0 = off)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write the last step's loss and a "
+                         "seeded sample of the updated state as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; a plain run does "
+                         "only what the headline figure needs (there is none "
+                         "today: the flag is accepted and changes nothing)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -179,11 +239,15 @@ def main() -> int:
 
     sync()
     t0 = time.time()
-    last_loss = 0.0
+    step_losses = []
     for _ in range(args.steps):
-        last_loss = float(engine.train_batch(it))
+        step_losses.append(float(engine.train_batch(it)))
+    last_loss = step_losses[-1]
     sync()
     elapsed = time.time() - t0
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, module, engine.optimizer, step_losses, rank, world)
 
     # MAX elapsed over ranks (ranks are barrier-synced; take max anyway)
     t = torch.tensor([elapsed], dtype=torch.float64)
