@@ -35,7 +35,8 @@ def build(verbose: bool = True, force: bool = False) -> Path:
     if not sources:
         raise RuntimeError(f"no HIP sources under {CSRC}")
     so_path = OUT_DIR / SO_NAME
-    if so_path.exists() and not force and so_path.stat().st_mtime >= _newest_mtime(sources):
+    inputs = [*sources, *CSRC.glob("*.h")]  # headers make the build stale too
+    if so_path.exists() and not force and so_path.stat().st_mtime >= _newest_mtime(inputs):
         return so_path
 
     import torch

@@ -37,6 +37,7 @@
 // forward's XOR layout), filled by the same in-register 4x4 dword
 // butterfly as the forward's V image.
 #include "common.h"
+#include "attn_order.h"
 
 namespace lpp {
 
@@ -164,7 +165,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE2, const float* __restrict__ Delta,
     short* __restrict__ dQ,
-    int B, int S, int H, int HKV, float c, float scale) {
+    int B, int S, int H, int HKV, float c, float scale,
+    int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NB = DBUF ? 2 : 1;
   // K@0 V@NB*16K Kt@2*NB*16K (+buf*16K each when double-buffered)
@@ -180,8 +182,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
   const int lq = lane & 31;
   const int hi2 = lane >> 5;
 
-  const int b = blockIdx.y / H;
-  const int h = blockIdx.y % H;
+  const AttnBlock ob = attn_block_order(blockIdx.x, (S + DQ_QB - 1) / DQ_QB, B * H,
+                                        order_G, ATTN_ORDER_FWD_DQ, order_mode);
+  const int qblk = ob.blk;
+  const int b = ob.head / H;
+  const int h = ob.head % H;
   const int hkv = h / (H / HKV);
   const int64_t sHD = (int64_t)H * AB_D;
   const int64_t sHkvD = (int64_t)HKV * AB_D;
@@ -189,7 +194,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
   const int64_t kv_base = (((int64_t)b * S) * HKV + hkv) * AB_D;
   const int64_t ld_base = ((int64_t)b * H + h) * S;
 
-  const int qw0 = blockIdx.x * DQ_QB + wid * DQ_QW;
+  const int qw0 = qblk * DQ_QB + wid * DQ_QW;
   const int qrow = qw0 + lq;
 
   bf16x8 qf[8], dof[8];
@@ -206,7 +211,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
 
   const int st_r = lane >> 4;
   const int st_c = 8 * (lane & 15);
-  const int kv_end = min(S, (int)(blockIdx.x + 1) * DQ_QB);
+  const int kv_end = min(S, (qblk + 1) * DQ_QB);
 
   auto ld_tile = [&](int kv0, int pass, bf16x8& kreg, bf16x8& vreg) {
     const int row = min(kv0 + 4 * wid + 32 * pass + st_r, S - 1);
@@ -380,7 +385,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE2, const float* __restrict__ Delta,
     short* __restrict__ dK, short* __restrict__ dV,
-    int B, int S, int H, int HKV, float c, float scale) {
+    int B, int S, int H, int HKV, float c, float scale,
+    int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NB = DBUF ? 2 : 1;
   // 64-row tiles, [128][64] transposed images (16 KB each):
@@ -405,14 +411,17 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
   const int l16 = lane & 15;
   const int hi4 = (lane >> 4) & 3;
 
-  const int b = blockIdx.y / HKV;
-  const int hkv = blockIdx.y % HKV;
+  const AttnBlock ob = attn_block_order(blockIdx.x, (S + KV_WG - 1) / KV_WG, B * HKV,
+                                        order_G, ATTN_ORDER_DKDV, order_mode);
+  const int kvblk = ob.blk;
+  const int b = ob.head / HKV;
+  const int hkv = ob.head % HKV;
   const int G = H / HKV;
   const int64_t sHD = (int64_t)H * AB_D;
   const int64_t sHkvD = (int64_t)HKV * AB_D;
   const int64_t kv_base = (((int64_t)b * S) * HKV + hkv) * AB_D;
 
-  const int kvw0 = blockIdx.x * KV_WG + wid * KV_KW;  // wave's 16 kv rows
+  const int kvw0 = kvblk * KV_WG + wid * KV_KW;  // wave's 16 kv rows
   const int kvrow = kvw0 + l16;                       // lane's kv row
 
   // K/V B-fragments (16x16x32: lane n = l16 = kv row, k = hi4*8+j)
@@ -434,7 +443,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
 
   const int st_r = (lane >> 4) & 3;
   const int st_c = 8 * (lane & 15);
-  const int qstart = blockIdx.x * KV_WG;
+  const int qstart = kvblk * KV_WG;
 
   for (int g = 0; g < G; ++g) {
     const int h = hkv * G + g;
@@ -578,65 +587,146 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
   }
 }
 
-}  // namespace lpp
-
-std::vector<at::Tensor> attention_bwd(at::Tensor dO, at::Tensor q, at::Tensor k,
-                                      at::Tensor v, at::Tensor o, at::Tensor lse2) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "attention_bwd: bf16 only");
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == lpp::AB_D, "attention_bwd: [B,S,H,128] required");
-  TORCH_CHECK(dO.is_contiguous() && q.is_contiguous() && k.is_contiguous() &&
-              v.is_contiguous() && o.is_contiguous() && lse2.is_contiguous());
-  const int B = q.size(0), S = q.size(1), H = q.size(2);
-  const int HKV = k.size(2);
-  TORCH_CHECK(H % HKV == 0);
-  auto stream = lpp::current_stream();
-
-  auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  {
-    const int64_t rows = (int64_t)B * S * H;
-    const int grid = lpp::grid_for(rows * 16, 256);
-    hipLaunchKernelGGL(lpp::attn_bwd_delta_kernel, dim3(grid), dim3(256), 0, stream,
-                       (const short*)dO.data_ptr(), (const short*)o.data_ptr(),
-                       delta.data_ptr<float>(), rows, S, H);
-    LPP_CHECK_HIP(hipGetLastError());
-  }
-
-  const float scale = 1.0f / std::sqrt((float)lpp::AB_D);
-  const float c = scale * 1.4426950408889634f;
-
-  auto dq = at::empty_like(q);
-  auto dk = at::empty_like(k);
-  auto dv = at::empty_like(v);
-
-  // LPP_ATTN_DBUF=1 restores the double-buffered (1 block/CU) variants;
-  // default is single-buffered at 2 blocks/CU (co-resident block hides the
-  // staging barriers).
+// ---- launches ----------------------------------------------------------------
+// LPP_ATTN_DBUF=1 restores the double-buffered (1 block/CU) variants;
+// default is single-buffered at 2 blocks/CU (co-resident block hides the
+// staging barriers).
+static bool attn_dbuf() {
   static const bool dbuf = [] {
     const char* e = getenv("LPP_ATTN_DBUF");
     return e && e[0] == '1';
   }();
-  {
-    const int qblocks = (S + lpp::DQ_QB - 1) / lpp::DQ_QB;
-    const size_t lds = dbuf ? 98304 : 49152;
-    auto kfn = dbuf ? lpp::attn_bwd_dq_kernel<true> : lpp::attn_bwd_dq_kernel<false>;
-    hipLaunchKernelGGL(kfn, dim3(qblocks, B * H), dim3(512), lds,
-                       stream, (const short*)q.data_ptr(), (const short*)k.data_ptr(),
-                       (const short*)v.data_ptr(), (const short*)dO.data_ptr(),
-                       lse2.data_ptr<float>(), delta.data_ptr<float>(),
-                       (short*)dq.data_ptr(), B, S, H, HKV, c, scale);
-    LPP_CHECK_HIP(hipGetLastError());
-  }
-  {
-    const int kvblocks = (S + lpp::KV_WG - 1) / lpp::KV_WG;
-    const size_t lds = dbuf ? (131072 + 1024) : (65536 + 512);
-    auto kfn = dbuf ? lpp::attn_bwd_dkdv_kernel<true> : lpp::attn_bwd_dkdv_kernel<false>;
-    hipLaunchKernelGGL(kfn, dim3(kvblocks, B * HKV), dim3(512), lds,
-                       stream, (const short*)q.data_ptr(), (const short*)k.data_ptr(),
-                       (const short*)v.data_ptr(), (const short*)dO.data_ptr(),
-                       lse2.data_ptr<float>(), delta.data_ptr<float>(),
-                       (short*)dk.data_ptr(), (short*)dv.data_ptr(), B, S, H, HKV, c,
-                       scale);
-    LPP_CHECK_HIP(hipGetLastError());
-  }
+  return dbuf;
+}
+
+void launch_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                     at::Tensor& o, at::Tensor& lse2, int order_mode, int order_G);
+
+static void launch_attn_bwd_delta(const at::Tensor& dO, const at::Tensor& o,
+                                  at::Tensor& delta) {
+  const int B = dO.size(0), S = dO.size(1), H = dO.size(2);
+  const int64_t rows = (int64_t)B * S * H;
+  const int grid = grid_for(rows * 16, 256);
+  hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3(grid), dim3(256), 0, current_stream(),
+                     (const short*)dO.data_ptr(), (const short*)o.data_ptr(),
+                     delta.data_ptr<float>(), rows, S, H);
+  LPP_CHECK_HIP(hipGetLastError());
+}
+
+// order_G <= 0 (both launches): heads per group from the resident workgroups
+// per XCD, 32 CUs x 2 blocks/CU single-buffered, x 1 double-buffered.
+static void launch_attn_bwd_dq(const at::Tensor& dO, const at::Tensor& q,
+                               const at::Tensor& k, const at::Tensor& v,
+                               const at::Tensor& lse2, const at::Tensor& delta,
+                               at::Tensor& dq, int order_mode, int order_G) {
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  const int HKV = k.size(2);
+  const float scale = 1.0f / std::sqrt((float)AB_D);
+  const float c = scale * 1.4426950408889634f;
+  const bool dbuf = attn_dbuf();
+  const int qblocks = (S + DQ_QB - 1) / DQ_QB;
+  if (order_G <= 0) order_G = attn_order_group(dbuf ? 32 : 64, qblocks);
+  const size_t lds = dbuf ? 98304 : 49152;
+  auto kfn = dbuf ? attn_bwd_dq_kernel<true> : attn_bwd_dq_kernel<false>;
+  hipLaunchKernelGGL(kfn, dim3(qblocks * B * H), dim3(512), lds,
+                     current_stream(), (const short*)q.data_ptr(), (const short*)k.data_ptr(),
+                     (const short*)v.data_ptr(), (const short*)dO.data_ptr(),
+                     lse2.data_ptr<float>(), delta.data_ptr<float>(),
+                     (short*)dq.data_ptr(), B, S, H, HKV, c, scale, order_mode, order_G);
+  LPP_CHECK_HIP(hipGetLastError());
+}
+
+static void launch_attn_bwd_dkdv(const at::Tensor& dO, const at::Tensor& q,
+                                 const at::Tensor& k, const at::Tensor& v,
+                                 const at::Tensor& lse2, const at::Tensor& delta,
+                                 at::Tensor& dk, at::Tensor& dv, int order_mode,
+                                 int order_G) {
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  const int HKV = k.size(2);
+  const float scale = 1.0f / std::sqrt((float)AB_D);
+  const float c = scale * 1.4426950408889634f;
+  const bool dbuf = attn_dbuf();
+  const int kvblocks = (S + KV_WG - 1) / KV_WG;
+  if (order_G <= 0) order_G = attn_order_group(dbuf ? 32 : 64, kvblocks);
+  const size_t lds = dbuf ? (131072 + 1024) : (65536 + 512);
+  auto kfn = dbuf ? attn_bwd_dkdv_kernel<true> : attn_bwd_dkdv_kernel<false>;
+  hipLaunchKernelGGL(kfn, dim3(kvblocks * B * HKV), dim3(512), lds,
+                     current_stream(), (const short*)q.data_ptr(), (const short*)k.data_ptr(),
+                     (const short*)v.data_ptr(), (const short*)dO.data_ptr(),
+                     lse2.data_ptr<float>(), delta.data_ptr<float>(),
+                     (short*)dk.data_ptr(), (short*)dv.data_ptr(), B, S, H, HKV, c,
+                     scale, order_mode, order_G);
+  LPP_CHECK_HIP(hipGetLastError());
+}
+
+}  // namespace lpp
+
+static void attention_bwd_check(const at::Tensor& dO, const at::Tensor& q,
+                                const at::Tensor& k, const at::Tensor& v,
+                                const at::Tensor& o, const at::Tensor& lse2) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "attention_bwd: bf16 only");
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == lpp::AB_D, "attention_bwd: [B,S,H,128] required");
+  TORCH_CHECK(dO.is_contiguous() && q.is_contiguous() && k.is_contiguous() &&
+              v.is_contiguous() && o.is_contiguous() && lse2.is_contiguous());
+  TORCH_CHECK(q.size(2) % k.size(2) == 0);
+}
+
+std::vector<at::Tensor> attention_bwd(at::Tensor dO, at::Tensor q, at::Tensor k,
+                                      at::Tensor v, at::Tensor o, at::Tensor lse2) {
+  attention_bwd_check(dO, q, k, v, o, lse2);
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
+  lpp::launch_attn_bwd_delta(dO, o, delta);
+  auto dq = at::empty_like(q);
+  auto dk = at::empty_like(k);
+  auto dv = at::empty_like(v);
+  const int mode = lpp::attn_order_mode();
+  lpp::launch_attn_bwd_dq(dO, q, k, v, lse2, delta, dq, mode ? lpp::ATTN_MODE1_DQ : 0, 0);
+  lpp::launch_attn_bwd_dkdv(dO, q, k, v, lse2, delta, dk, dv,
+                            mode ? lpp::ATTN_MODE1_DKDV : 0, 0);
   return {dq, dk, dv};
+}
+
+// Device-timed A/B of one attention kernel under an explicit block order:
+// kernel "fwd" | "dq" | "dkdv", order (mode, G; G <= 0 = the computed group).
+// One hipEvent pair per launch; returns the ms of each of `reps` launches
+// after `warmup` untimed ones.
+std::vector<double> attention_time_kernel(std::string kernel, at::Tensor dO, at::Tensor q,
+                                          at::Tensor k, at::Tensor v, at::Tensor o,
+                                          at::Tensor lse2, int64_t mode, int64_t G,
+                                          int64_t warmup, int64_t reps) {
+  attention_bwd_check(dO, q, k, v, o, lse2);
+  TORCH_CHECK(mode == 0 || mode == 1, "attention_time_kernel: mode 0 or 1");
+  TORCH_CHECK(kernel == "fwd" || kernel == "dq" || kernel == "dkdv",
+              "attention_time_kernel: kernel is fwd, dq or dkdv");
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
+  lpp::launch_attn_bwd_delta(dO, o, delta);
+  auto o2 = at::empty_like(q), dq = at::empty_like(q);
+  auto lse_out = at::empty_like(lse2);
+  auto dk = at::empty_like(k), dv = at::empty_like(v);
+  auto launch = [&] {
+    if (kernel == "fwd") lpp::launch_attn_fwd(q, k, v, o2, lse_out, (int)mode, (int)G);
+    else if (kernel == "dq")
+      lpp::launch_attn_bwd_dq(dO, q, k, v, lse2, delta, dq, (int)mode, (int)G);
+    else lpp::launch_attn_bwd_dkdv(dO, q, k, v, lse2, delta, dk, dv, (int)mode, (int)G);
+  };
+  auto stream = lpp::current_stream();
+  hipEvent_t e0, e1;
+  LPP_CHECK_HIP(hipEventCreate(&e0));
+  LPP_CHECK_HIP(hipEventCreate(&e1));
+  for (int64_t i = 0; i < warmup; ++i) launch();
+  std::vector<double> ms;
+  for (int64_t i = 0; i < reps; ++i) {
+    LPP_CHECK_HIP(hipEventRecord(e0, stream));
+    launch();
+    LPP_CHECK_HIP(hipEventRecord(e1, stream));
+    LPP_CHECK_HIP(hipEventSynchronize(e1));
+    float t = 0.f;
+    LPP_CHECK_HIP(hipEventElapsedTime(&t, e0, e1));
+    ms.push_back(t);
+  }
+  LPP_CHECK_HIP(hipEventDestroy(e0));
+  LPP_CHECK_HIP(hipEventDestroy(e1));
+  return ms;
 }

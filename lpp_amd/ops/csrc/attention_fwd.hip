@@ -30,6 +30,7 @@
 //   - outputs: O bf16 and LSE2[B,H,S] fp32 (base-2 logsumexp of the
 //     scaled scores; consumed by the backward kernels)
 #include "common.h"
+#include "attn_order.h"
 
 namespace lpp {
 
@@ -64,7 +65,8 @@ __device__ __forceinline__ int as_i(float v) { return __float_as_int(v); }
 __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, short* __restrict__ O, float* __restrict__ LSE2,
-    int B, int S, int H, int HKV, float c /* scale*log2e */) {
+    int B, int S, int H, int HKV, float c /* scale*log2e */,
+    int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // buffer layout: K0 @0, K1 @16K, Vt0 @32K, Vt1 @48K
   auto k_lds = [&](int buf) -> char* { return smem + buf * 16384; };
@@ -76,8 +78,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
   const int lq = lane & 31;        // this lane's q row (within the wave)
   const int hi2 = lane >> 5;
 
-  const int qblk = blockIdx.x;
-  const int bh = blockIdx.y;
+  const AttnBlock ob = attn_block_order(blockIdx.x, (S + AF_QB - 1) / AF_QB, B * H,
+                                        order_G, ATTN_ORDER_FWD_DQ, order_mode);
+  const int qblk = ob.blk;
+  const int bh = ob.head;
   const int b = bh / H;
   const int h = bh % H;
   const int hkv = h / (H / HKV);
@@ -323,6 +327,33 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     LSE2[((int64_t)b * H + h) * S + qrow] = m_run + log2f(l_run);
 }
 
+// ---- block-order state and launch -------------------------------------------
+static int g_order_mode = [] {
+  const char* e = getenv("LPP_ATTN_ORDER");
+  return (e && e[0] == '0') ? 0 : 1;
+}();
+
+int attn_order_mode() { return g_order_mode; }
+
+// order_G <= 0: heads per group from the resident workgroups per XCD
+// (32 CUs x 2 blocks/CU at 64 KB LDS).
+void launch_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                     at::Tensor& o, at::Tensor& lse2, int order_mode, int order_G) {
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  const int HKV = k.size(2);
+  const float scale = 1.0f / std::sqrt((float)AF_D);
+  const float c = scale * 1.4426950408889634f;  // log2(e)
+  const int qblocks = (S + AF_QB - 1) / AF_QB;
+  if (order_G <= 0) order_G = attn_order_group(64, qblocks);
+  const size_t lds = 65536;
+  hipLaunchKernelGGL(attn_fwd_kernel, dim3(qblocks * B * H), dim3(512), lds,
+                     current_stream(), (const short*)q.data_ptr(),
+                     (const short*)k.data_ptr(), (const short*)v.data_ptr(),
+                     (short*)o.data_ptr(), lse2.data_ptr<float>(), B, S, H, HKV, c,
+                     order_mode, order_G);
+  LPP_CHECK_HIP(hipGetLastError());
+}
+
 }  // namespace lpp
 
 std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v) {
@@ -334,14 +365,34 @@ std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v) 
   TORCH_CHECK(H % HKV == 0);
   auto o = at::empty_like(q);
   auto lse2 = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  const float scale = 1.0f / std::sqrt((float)lpp::AF_D);
-  const float c = scale * 1.4426950408889634f;  // log2(e)
-  const int qblocks = (S + lpp::AF_QB - 1) / lpp::AF_QB;
-  const size_t lds = 65536;
-  hipLaunchKernelGGL(lpp::attn_fwd_kernel, dim3(qblocks, B * H), dim3(512), lds,
-                     lpp::current_stream(), (const short*)q.data_ptr(),
-                     (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                     (short*)o.data_ptr(), lse2.data_ptr<float>(), B, S, H, HKV, c);
-  LPP_CHECK_HIP(hipGetLastError());
+  lpp::launch_attn_fwd(q, k, v, o, lse2,
+                       lpp::attn_order_mode() ? lpp::ATTN_MODE1_FWD : 0, 0);
   return {o, lse2};
+}
+
+void attention_set_block_order(int64_t mode) {
+  TORCH_CHECK(mode == 0 || mode == 1, "attention_set_block_order: mode 0 or 1");
+  lpp::g_order_mode = (int)mode;
+}
+
+int64_t attention_get_block_order() { return lpp::g_order_mode; }
+
+// Host only: the (blk, head) pairs of L = 0..n-1 from the header function the
+// kernels run.  kind 0 = fwd/dQ, 1 = dK/dV.
+at::Tensor attention_block_order(int64_t kind, int64_t nblk, int64_t nheads, int64_t G,
+                                 int64_t mode) {
+  TORCH_CHECK(kind == 0 || kind == 1, "attention_block_order: kind 0 (fwd/dQ) or 1 (dK/dV)");
+  TORCH_CHECK(mode == 0 || mode == 1, "attention_block_order: mode 0 or 1");
+  TORCH_CHECK(nblk >= 1 && nheads >= 1 && nblk * nheads < (int64_t)1 << 30 && G >= 1);
+  G = std::min(G, nheads);
+  const int n = (int)(nblk * nheads);
+  auto out = at::empty({n, 2}, at::TensorOptions().dtype(at::kInt));
+  int* p = out.data_ptr<int>();
+  for (int L = 0; L < n; ++L) {
+    const lpp::AttnBlock ob =
+        lpp::attn_block_order(L, (int)nblk, (int)nheads, (int)G, (int)kind, (int)mode);
+    p[2 * L] = ob.blk;
+    p[2 * L + 1] = ob.head;
+  }
+  return out;
 }

@@ -18,6 +18,14 @@ at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor labels, at::Tensor ls
 std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v);
 std::vector<at::Tensor> attention_bwd(at::Tensor dO, at::Tensor q, at::Tensor k,
                                       at::Tensor v, at::Tensor o, at::Tensor lse2);
+void attention_set_block_order(int64_t mode);
+int64_t attention_get_block_order();
+at::Tensor attention_block_order(int64_t kind, int64_t nblk, int64_t nheads, int64_t G,
+                                 int64_t mode);
+std::vector<double> attention_time_kernel(std::string kernel, at::Tensor dO, at::Tensor q,
+                                          at::Tensor k, at::Tensor v, at::Tensor o,
+                                          at::Tensor lse2, int64_t mode, int64_t G,
+                                          int64_t warmup, int64_t reps);
 at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B);
 void wgrad_f32_accum(at::Tensor x, at::Tensor dy, at::Tensor dw);
 void wgrad_f32_accum_pre(at::Tensor xT, at::Tensor dyT, at::Tensor dw);
@@ -51,6 +59,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adamw", &fused_adamw, "fused mixed-precision AdamW");
   m.def("attention_fwd", &attention_fwd, "flash causal attention forward (O, LSE2)");
   m.def("attention_bwd", &attention_bwd, "flash causal attention backward (dQ, dK, dV)");
+  m.def("attention_set_block_order", &attention_set_block_order,
+        "attention block order: 0 = legacy, 1 = XCD-balanced heavy-first (default, "
+        "LPP_ATTN_ORDER)", py::arg("mode"));
+  m.def("attention_get_block_order", &attention_get_block_order, "current order mode");
+  m.def("attention_block_order", &attention_block_order,
+        "host: [n,2] int (blk, head) of linear block ids 0..n-1; kind 0 fwd/dQ, 1 dK/dV",
+        py::arg("kind"), py::arg("nblk"), py::arg("nheads"), py::arg("G"), py::arg("mode"));
+  m.def("attention_time_kernel", &attention_time_kernel,
+        "hipEvent ms per launch of one attention kernel (fwd|dq|dkdv) under an explicit "
+        "block order", py::arg("kernel"), py::arg("dO"), py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("o"), py::arg("lse2"), py::arg("mode"), py::arg("G") = 0,
+        py::arg("warmup") = 3, py::arg("reps") = 20);
   m.def("wgrad_f32_accum", &wgrad_f32_accum, "dW_f32 += dY^T @ X (hipBLASLt, beta=1)");
   m.def("wgrad_f32_accum_pre", &wgrad_f32_accum_pre,
         "dW_f32 += dyT @ xT^T, pre-transposed k-contiguous operands (hipBLASLt, beta=1)");
