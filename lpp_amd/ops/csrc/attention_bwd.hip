@@ -21,7 +21,8 @@
 //        P    = exp2(c*S^T - L[own q]);  dS = P*(dP^T - delta[own q])
 //        dQ  += mfma(pack(dS), K^T image)          (scale at epilogue)
 //   3. dK/dV kernel — 8 waves x 16 kv rows (lane = kv, 16x16x32
-//      fragments), 2 waves/SIMD; grid over KV blocks x B*HKV; per
+//      fragments), 2 waves/SIMD (one workgroup per CU); grid over KV blocks
+//      x B*HKV; per
 //      double-buffered 64-row q tile (two 32-row compute halves):
 //        S    = mfma(Q_lds, K_reg)   C[q regs][kv lane]
 //        dP   = mfma(dO_lds, V_reg)  same layout
@@ -156,10 +157,16 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(
 // double-buffered K (normal), V (normal), K^T (tswz image).
 constexpr int DQ_QW = 32, DQ_WAVES = 8, DQ_QB = 256, DQ_KVB = 64;
 
-// DBUF=true: double-buffered images (96 KB LDS, 1 block/CU, one barrier
-// per tile).  DBUF=false: single-buffered (48 KB, 2 blocks/CU, two
-// barriers per tile) — staging stalls hidden by the co-resident block.
-template <bool DBUF>
+// Double-buffered images (96 KB LDS): staging runs one tile ahead and the
+// loop has one barrier per tile.  After the barrier of tile t the registers
+// holding tile t+1 are written into the other buffer and the global loads of
+// tile t+2 are issued; no barrier separates those LDS writes from tile t's
+// MFMAs.  The wave id is read into a scalar register, so the tile class
+// (past the diagonal / masked / interior) is a scalar branch; interior tiles
+// (entirely below the wave's diagonal and inside S) run a straight-line
+// softmax, diagonal and tail tiles the masked form.
+// gfx950 (hipcc -O3): NumVgprs 254, ScratchSize 0, Occupancy 2 waves/SIMD.
+// 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
 __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
@@ -168,16 +175,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
     int B, int S, int H, int HKV, float c, float scale,
     int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NB = DBUF ? 2 : 1;
-  // K@0 V@NB*16K Kt@2*NB*16K (+buf*16K each when double-buffered)
-  auto k_lds = [&](int buf) -> char* { return smem + (DBUF ? buf : 0) * 16384; };
-  auto v_lds = [&](int buf) -> char* {
-    return smem + NB * 16384 + (DBUF ? buf : 0) * 16384; };
-  auto kt_lds = [&](int buf) -> char* {
-    return smem + 2 * NB * 16384 + (DBUF ? buf : 0) * 16384; };
+  // K@0 V@32K Kt@64K (+buf*16K each)
+  auto k_lds = [&](int buf) -> char* { return smem + buf * 16384; };
+  auto v_lds = [&](int buf) -> char* { return smem + 32768 + buf * 16384; };
+  auto kt_lds = [&](int buf) -> char* { return smem + 65536 + buf * 16384; };
 
   const int tid = threadIdx.x;
-  const int wid = tid >> 6;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar
   const int lane = tid & 63;
   const int lq = lane & 31;
   const int hi2 = lane >> 5;
@@ -239,91 +243,82 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
   ld_tile(0, 1, kreg1, vreg1);
   write_tile(0, 0, kreg0, vreg0);
   write_tile(0, 1, kreg1, vreg1);
-  if (DBUF && DQ_KVB < kv_end) {  // T14: pre-load tile 1 to registers
+  if (DQ_KVB < kv_end) {  // T14: pre-load tile 1 to registers
     ld_tile(DQ_KVB, 0, kreg0, vreg0);
     ld_tile(DQ_KVB, 1, kreg1, vreg1);
   }
   __syncthreads();
 
   for (int kv0 = 0, cur = 0; kv0 < kv_end; kv0 += DQ_KVB, cur ^= 1) {
-    const bool have_next = kv0 + DQ_KVB < kv_end;
-    if (DBUF) {
-      // T14 write-after-barrier: tile t+1 (in registers) written into the
-      // other buffer right after the barrier, overlapping this tile's
-      // MFMAs; tile t+2's loads re-issue immediately.
-      if (have_next) {
-        write_tile(cur ^ 1, 0, kreg0, vreg0);
-        write_tile(cur ^ 1, 1, kreg1, vreg1);
-        if (kv0 + 2 * DQ_KVB < kv_end) {
-          ld_tile(kv0 + 2 * DQ_KVB, 0, kreg0, vreg0);
-          ld_tile(kv0 + 2 * DQ_KVB, 1, kreg1, vreg1);
-        }
+    // T14 write-after-barrier: tile t+1 (in registers) goes into the other
+    // buffer after the barrier and tile t+2's loads re-issue at once.
+    if (kv0 + DQ_KVB < kv_end) {
+      write_tile(cur ^ 1, 0, kreg0, vreg0);
+      write_tile(cur ^ 1, 1, kreg1, vreg1);
+      if (kv0 + 2 * DQ_KVB < kv_end) {
+        ld_tile(kv0 + 2 * DQ_KVB, 0, kreg0, vreg0);
+        ld_tile(kv0 + 2 * DQ_KVB, 1, kreg1, vreg1);
       }
-    } else if (have_next) {
-      ld_tile(kv0 + DQ_KVB, 0, kreg0, vreg0);
-      ld_tile(kv0 + DQ_KVB, 1, kreg1, vreg1);
     }
 
     if (kv0 < qw0 + DQ_QW) {
-      f32x16 st[2], dpt[2];
+      // wave-uniform tile class: interior tiles take the straight-line form
+      const bool need_mask = (kv0 + DQ_KVB > qw0) || (kv0 + DQ_KVB > S);
+      // The tile runs as two independent 32-key halves, so only one half's
+      // S^T/dP^T accumulators are live at a time and one half's softmax can
+      // sit under the other half's MFMAs.  Each st/dpt element still sums
+      // dc = 0..7 and each dq_acc element ks = 0..3, in that order.
 #pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2)
+      for (int t2 = 0; t2 < 2; ++t2) {
+        f32x16 st, dpt;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { st[t2][r] = 0.f; dpt[t2][r] = 0.f; }
-      __builtin_amdgcn_s_setprio(1);  // favour the MFMA cluster (guide T5)
+        for (int r = 0; r < 16; ++r) { st[r] = 0.f; dpt[r] = 0.f; }
+        __builtin_amdgcn_s_setprio(1);  // favour the MFMA cluster (guide T5)
 #pragma unroll
-      for (int dc = 0; dc < 8; ++dc) {
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2) {
+        for (int dc = 0; dc < 8; ++dc) {
           const bf16x8 ak = *reinterpret_cast<const bf16x8*>(
               k_lds(cur) + bswz(t2 * 32 + lq, dc * 16 + hi2 * 8));
           const bf16x8 av = *reinterpret_cast<const bf16x8*>(
               v_lds(cur) + bswz(t2 * 32 + lq, dc * 16 + hi2 * 8));
-          st[t2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, qf[dc], st[t2], 0, 0, 0);
-          dpt[t2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, dof[dc], dpt[t2], 0, 0, 0);
+          st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, qf[dc], st, 0, 0, 0);
+          dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, dof[dc], dpt, 0, 0, 0);
         }
-      }
-      __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
 
-      const bool need_mask = (kv0 + DQ_KVB > qw0) || (kv0 + DQ_KVB > S);
-      float ds[32];
+        float ds[16];
+        if (need_mask) {
 #pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          bool ok = true;
-          if (need_mask) {
+          for (int r = 0; r < 16; ++r) {
             const int kv = kv0 + t2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi2;
-            ok = (kv <= qrow) && (kv < S);
+            const bool ok = (kv <= qrow) && (kv < S);
+            const float e = exp2f(fmaf(st[r], c, -Lq));
+            ds[r] = (ok ? e : 0.f) * (dpt[r] - Dq);
           }
-          const float p = ok ? exp2f(fmaf(st[t2][r], c, -Lq)) : 0.f;
-          ds[t2 * 16 + r] = p * (dpt[t2][r] - Dq);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            ds[r] = exp2f(fmaf(st[r], c, -Lq)) * (dpt[r] - Dq);
         }
 
-      bf16x8 dsa[4];
-      pack_pair(&ds[0], &dsa[0]);
-      pack_pair(&ds[16], &dsa[2]);
+        bf16x8 dsa[2];
+        pack_pair(ds, dsa);
 
-      __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const int d = dt * 32 + lq;
+        for (int dt = 0; dt < 4; ++dt) {
+          const int d = dt * 32 + lq;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const bf16x8 bk = *reinterpret_cast<const bf16x8*>(
-              kt_lds(cur) + tswz(d, ks * 16 + hi2 * 8));
-          dq_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[ks], bk, dq_acc[dt], 0, 0, 0);
+          for (int ks = 0; ks < 2; ++ks) {
+            const bf16x8 bk = *reinterpret_cast<const bf16x8*>(
+                kt_lds(cur) + tswz(d, (2 * t2 + ks) * 16 + hi2 * 8));
+            dq_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[ks], bk, dq_acc[dt], 0, 0, 0);
+          }
         }
+        __builtin_amdgcn_s_setprio(0);
       }
-      __builtin_amdgcn_s_setprio(0);
     }
 
-    if (!DBUF && have_next) {
-      __syncthreads();  // everyone done reading the only buffer
-      write_tile(0, 0, kreg0, vreg0);
-      write_tile(0, 1, kreg1, vreg1);
-    }
-    __syncthreads();
+    __syncthreads();  // the one barrier per tile, outside every wave condition
   }
 
 #pragma unroll
@@ -379,7 +374,11 @@ __device__ __forceinline__ bf16x8 pack_frag16(const float p[2][4], int hi4_odd) 
   return *reinterpret_cast<const bf16x8*>(w);
 }
 
-template <bool DBUF>
+// Same pipeline as the dQ kernel: double-buffered images (129 KB LDS), staging
+// one tile ahead, one barrier per tile, scalar wave id, straight-line softmax
+// on the half-tiles that need no mask.
+// gfx950 (hipcc -O3): NumVgprs 220, ScratchSize 0, Occupancy 2 waves/SIMD.
+// 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
 __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
@@ -388,25 +387,19 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
     int B, int S, int H, int HKV, float c, float scale,
     int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NB = DBUF ? 2 : 1;
-  // 64-row tiles, [128][64] transposed images (16 KB each):
-  // Q@0 dO@NB*16K Qt@2*NB*16K dOt@3*NB*16K L/D@4*NB*16K
-  auto q_lds = [&](int buf) -> char* { return smem + (DBUF ? buf : 0) * 16384; };
-  auto do_lds = [&](int buf) -> char* {
-    return smem + NB * 16384 + (DBUF ? buf : 0) * 16384; };
-  auto qt_lds = [&](int buf) -> char* {
-    return smem + 2 * NB * 16384 + (DBUF ? buf : 0) * 16384; };
-  auto dot_lds = [&](int buf) -> char* {
-    return smem + 3 * NB * 16384 + (DBUF ? buf : 0) * 16384; };
+  // 64-row tiles, [128][64] transposed images (16 KB each, +buf*16K):
+  // Q@0 dO@32K Qt@64K dOt@96K L@128K D@128K+512
+  auto q_lds = [&](int buf) -> char* { return smem + buf * 16384; };
+  auto do_lds = [&](int buf) -> char* { return smem + 32768 + buf * 16384; };
+  auto qt_lds = [&](int buf) -> char* { return smem + 65536 + buf * 16384; };
+  auto dot_lds = [&](int buf) -> char* { return smem + 98304 + buf * 16384; };
   auto l_buf = [&](int buf) -> float* {
-    return reinterpret_cast<float*>(smem + 4 * NB * 16384) + (DBUF ? buf : 0) * 64; };
+    return reinterpret_cast<float*>(smem + 131072) + buf * 64; };
   auto d_buf = [&](int buf) -> float* {
-    return reinterpret_cast<float*>(smem + 4 * NB * 16384 + NB * 256) +
-           (DBUF ? buf : 0) * 64; };
-
+    return reinterpret_cast<float*>(smem + 131072 + 512) + buf * 64; };
 
   const int tid = threadIdx.x;
-  const int wid = tid >> 6;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar
   const int lane = tid & 63;
   const int l16 = lane & 15;
   const int hi4 = (lane >> 4) & 3;
@@ -478,27 +471,21 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
     ld_tile(qstart, 1, qreg1, dreg1);
     write_tile(0, qstart, 0, qreg0, dreg0);
     write_tile(0, qstart, 1, qreg1, dreg1);
-    if (DBUF && qstart + KV_QT < S) {  // T14: pre-load tile 1 to registers
+    if (qstart + KV_QT < S) {  // T14: pre-load tile 1 to registers
       ld_tile(qstart + KV_QT, 0, qreg0, dreg0);
       ld_tile(qstart + KV_QT, 1, qreg1, dreg1);
     }
     __syncthreads();
 
     for (int qt0 = qstart, cur = 0; qt0 < S; qt0 += KV_QT, cur ^= 1) {
-      const bool have_next = qt0 + KV_QT < S;
-      if (DBUF) {
-        // T14 write-after-barrier (see dq kernel)
-        if (have_next) {
-          write_tile(cur ^ 1, qt0 + KV_QT, 0, qreg0, dreg0);
-          write_tile(cur ^ 1, qt0 + KV_QT, 1, qreg1, dreg1);
-          if (qt0 + 2 * KV_QT < S) {
-            ld_tile(qt0 + 2 * KV_QT, 0, qreg0, dreg0);
-            ld_tile(qt0 + 2 * KV_QT, 1, qreg1, dreg1);
-          }
+      // T14 write-after-barrier (see dq kernel)
+      if (qt0 + KV_QT < S) {
+        write_tile(cur ^ 1, qt0 + KV_QT, 0, qreg0, dreg0);
+        write_tile(cur ^ 1, qt0 + KV_QT, 1, qreg1, dreg1);
+        if (qt0 + 2 * KV_QT < S) {
+          ld_tile(qt0 + 2 * KV_QT, 0, qreg0, dreg0);
+          ld_tile(qt0 + 2 * KV_QT, 1, qreg1, dreg1);
         }
-      } else if (have_next) {
-        ld_tile(qt0 + KV_QT, 0, qreg0, dreg0);
-        ld_tile(qt0 + KV_QT, 1, qreg1, dreg1);
       }
 
       if (qt0 + KV_QT - 1 >= kvw0) {
@@ -526,6 +513,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
           }
           __builtin_amdgcn_s_setprio(0);
 
+          // wave-uniform tile class.  An interior half-tile has
+          // kvrow < qh0 and qh0 + 32 <= S, so every lane's kv row is inside S
+          // and no element needs a mask: straight-line form.
           const bool need_mask = (qh0 < kvw0 + KV_KW) || (qh0 + 32 > S);
           float p[2][4], ds[2][4];
 #pragma unroll
@@ -533,15 +523,21 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
             const int q0 = half * 32 + qs * 16 + hi4 * 4;
             const f32x4 Lr = *reinterpret_cast<const f32x4*>(&l_buf(cur)[q0]);
             const f32x4 Dr = *reinterpret_cast<const f32x4*>(&d_buf(cur)[q0]);
+            if (need_mask) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              bool ok = (kvrow < S);
-              if (need_mask) {
+              for (int r = 0; r < 4; ++r) {
                 const int q = qt0 + q0 + r;
-                ok = ok && (q >= kvrow) && (q < S);
+                const bool ok = (kvrow < S) && (q >= kvrow) && (q < S);
+                const float e = exp2f(fmaf(st[qs][r], c, -Lr[r]));
+                p[qs][r] = ok ? e : 0.f;
+                ds[qs][r] = p[qs][r] * (dpt[qs][r] - Dr[r]);
               }
-              p[qs][r] = ok ? exp2f(fmaf(st[qs][r], c, -Lr[r])) : 0.f;
-              ds[qs][r] = p[qs][r] * (dpt[qs][r] - Dr[r]);
+            } else {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                p[qs][r] = exp2f(fmaf(st[qs][r], c, -Lr[r]));
+                ds[qs][r] = p[qs][r] * (dpt[qs][r] - Dr[r]);
+              }
             }
           }
 
@@ -564,12 +560,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
         }
       }
 
-      if (!DBUF && have_next) {
-        __syncthreads();  // everyone done reading the only buffer
-        write_tile(0, qt0 + KV_QT, 0, qreg0, dreg0);
-        write_tile(0, qt0 + KV_QT, 1, qreg1, dreg1);
-      }
-      __syncthreads();
+      __syncthreads();  // the one barrier per tile, outside every wave condition
     }
     __syncthreads();  // buffer 0 reuse across g
   }
@@ -588,17 +579,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
 }
 
 // ---- launches ----------------------------------------------------------------
-// LPP_ATTN_DBUF=1 restores the double-buffered (1 block/CU) variants;
-// default is single-buffered at 2 blocks/CU (co-resident block hides the
-// staging barriers).
-static bool attn_dbuf() {
-  static const bool dbuf = [] {
-    const char* e = getenv("LPP_ATTN_DBUF");
-    return e && e[0] == '1';
-  }();
-  return dbuf;
-}
-
 void launch_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                      at::Tensor& o, at::Tensor& lse2, int order_mode, int order_G);
 
@@ -613,8 +593,10 @@ static void launch_attn_bwd_delta(const at::Tensor& dO, const at::Tensor& o,
   LPP_CHECK_HIP(hipGetLastError());
 }
 
-// order_G <= 0 (both launches): heads per group from the resident workgroups
-// per XCD, 32 CUs x 2 blocks/CU single-buffered, x 1 double-buffered.
+// order_G <= 0 (both launches): heads per group = ATTN_GROUP_WAVES resident
+// waves of workgroups per XCD (32 CUs x one workgroup per CU) over nblk; the
+// factor is the measured winner of the G sweep, not a residency
+// (profiles/README.md, Round 4).
 static void launch_attn_bwd_dq(const at::Tensor& dO, const at::Tensor& q,
                                const at::Tensor& k, const at::Tensor& v,
                                const at::Tensor& lse2, const at::Tensor& delta,
@@ -623,12 +605,11 @@ static void launch_attn_bwd_dq(const at::Tensor& dO, const at::Tensor& q,
   const int HKV = k.size(2);
   const float scale = 1.0f / std::sqrt((float)AB_D);
   const float c = scale * 1.4426950408889634f;
-  const bool dbuf = attn_dbuf();
   const int qblocks = (S + DQ_QB - 1) / DQ_QB;
-  if (order_G <= 0) order_G = attn_order_group(dbuf ? 32 : 64, qblocks);
-  const size_t lds = dbuf ? 98304 : 49152;
-  auto kfn = dbuf ? attn_bwd_dq_kernel<true> : attn_bwd_dq_kernel<false>;
-  hipLaunchKernelGGL(kfn, dim3(qblocks * B * H), dim3(512), lds,
+  if (order_G <= 0)
+    order_G = attn_order_group(ATTN_GROUP_WAVES * ATTN_RESIDENT_PER_XCD, qblocks);
+  const size_t lds = 98304;
+  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(qblocks * B * H), dim3(512), lds,
                      current_stream(), (const short*)q.data_ptr(), (const short*)k.data_ptr(),
                      (const short*)v.data_ptr(), (const short*)dO.data_ptr(),
                      lse2.data_ptr<float>(), delta.data_ptr<float>(),
@@ -645,12 +626,11 @@ static void launch_attn_bwd_dkdv(const at::Tensor& dO, const at::Tensor& q,
   const int HKV = k.size(2);
   const float scale = 1.0f / std::sqrt((float)AB_D);
   const float c = scale * 1.4426950408889634f;
-  const bool dbuf = attn_dbuf();
   const int kvblocks = (S + KV_WG - 1) / KV_WG;
-  if (order_G <= 0) order_G = attn_order_group(dbuf ? 32 : 64, kvblocks);
-  const size_t lds = dbuf ? (131072 + 1024) : (65536 + 512);
-  auto kfn = dbuf ? attn_bwd_dkdv_kernel<true> : attn_bwd_dkdv_kernel<false>;
-  hipLaunchKernelGGL(kfn, dim3(kvblocks * B * HKV), dim3(512), lds,
+  if (order_G <= 0)
+    order_G = attn_order_group(ATTN_GROUP_WAVES * ATTN_RESIDENT_PER_XCD, kvblocks);
+  const size_t lds = 131072 + 1024;
+  hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3(kvblocks * B * HKV), dim3(512), lds,
                      current_stream(), (const short*)q.data_ptr(), (const short*)k.data_ptr(),
                      (const short*)v.data_ptr(), (const short*)dO.data_ptr(),
                      lse2.data_ptr<float>(), delta.data_ptr<float>(),

@@ -62,6 +62,7 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
 __device__ __forceinline__ float as_f(int v) { return __int_as_float(v); }
 __device__ __forceinline__ int as_i(float v) { return __float_as_int(v); }
 
+// 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
 __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, short* __restrict__ O, float* __restrict__ LSE2,
@@ -335,8 +336,9 @@ static int g_order_mode = [] {
 
 int attn_order_mode() { return g_order_mode; }
 
-// order_G <= 0: heads per group from the resident workgroups per XCD
-// (32 CUs x 2 blocks/CU at 64 KB LDS).
+// order_G <= 0: heads per group = ATTN_GROUP_WAVES resident waves of
+// workgroups per XCD (32 CUs x one workgroup per CU: 231 VGPRs, 2 waves/SIMD)
+// over nblk; the factor is the G sweep's winner (attn_order.h).
 void launch_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                      at::Tensor& o, at::Tensor& lse2, int order_mode, int order_G) {
   const int B = q.size(0), S = q.size(1), H = q.size(2);
@@ -344,7 +346,8 @@ void launch_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor&
   const float scale = 1.0f / std::sqrt((float)AF_D);
   const float c = scale * 1.4426950408889634f;  // log2(e)
   const int qblocks = (S + AF_QB - 1) / AF_QB;
-  if (order_G <= 0) order_G = attn_order_group(64, qblocks);
+  if (order_G <= 0)
+    order_G = attn_order_group(ATTN_GROUP_WAVES * ATTN_RESIDENT_PER_XCD, qblocks);
   const size_t lds = 65536;
   hipLaunchKernelGGL(attn_fwd_kernel, dim3(qblocks * B * H), dim3(512), lds,
                      current_stream(), (const short*)q.data_ptr(),

@@ -65,8 +65,18 @@ LPP_HD inline AttnBlock attn_block_order(int L, int nblk, int nheads, int G, int
   return {kind == ATTN_ORDER_FWD_DQ ? nblk - 1 - rank : rank, grp * G + rem % Gl};
 }
 
-// Heads per group: one full wave of resident workgroups per XCD
-// (CUs per XCD x blocks per CU) spans whole groups.
+// Resident workgroups per XCD: 32 CUs x one 512-thread workgroup per CU.  All
+// three attention kernels need more than 128 VGPRs, so they run at
+// 2 waves/SIMD, which one 8-wave workgroup fills.
+constexpr int ATTN_RESIDENT_PER_XCD = 32;
+// The launches size a group to span this many resident waves of workgroups.
+// Measured, not derived (G sweeps at B=4, S=4096, H=64, profiles/README.md
+// Round 4): fwd and dQ (nblk 16) are best at G = 8, dK/dV (nblk 32) at G = 4,
+// i.e. 4 waves each; the one-wave G is 7-9% slower, the two-wave G 0.4-2%.
+constexpr int ATTN_GROUP_WAVES = 4;
+
+// Heads per group: the groups that `resident_per_xcd` workgroups span, rounded
+// up to whole heads.
 inline int attn_order_group(int resident_per_xcd, int nblk) {
   const int g = (resident_per_xcd + nblk - 1) / nblk;
   return g < 1 ? 1 : g;
