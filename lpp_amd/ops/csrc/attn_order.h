@@ -82,9 +82,6 @@ inline int attn_order_group(int resident_per_xcd, int nblk) {
   return g < 1 ? 1 : g;
 }
 
-// Process-wide order mode (LPP_ATTN_ORDER, default 1; see attention_fwd.hip).
-int attn_order_mode();
-
 // The order each kernel runs under process mode 1: the measured winner per
 // kernel (profiles/README.md, Round 3).  0 = that kernel keeps the legacy order.
 constexpr int ATTN_MODE1_FWD = 1;

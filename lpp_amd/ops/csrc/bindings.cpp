@@ -40,6 +40,9 @@ void wgrad_set_algo(int64_t T, int64_t in, int64_t out, int64_t index, int64_t k
 std::tuple<int64_t, std::string> wgrad_current_algo(int64_t T, int64_t in, int64_t out,
                                                     int64_t kind);
 at::Tensor mfma_test_32x32x16(at::Tensor A, at::Tensor B);
+std::vector<at::Tensor> attn_tile_test_roundtrip(at::Tensor tile);
+at::Tensor attn_tile_test_pack_pair(at::Tensor x);
+at::Tensor attn_tile_test_pack_frag16(at::Tensor x);
 void fused_adamw(std::vector<at::Tensor> params, std::vector<at::Tensor> masters,
                  std::vector<at::Tensor> grads, std::vector<at::Tensor> exp_avg,
                  std::vector<at::Tensor> exp_avg_sq, double lr, double beta1, double beta2,
@@ -88,4 +91,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("T"), py::arg("in_dim"), py::arg("out"), py::arg("kind") = 0);
   m.def("mfma_test_16x16x32", &mfma_test_16x16x32, "MFMA layout validation");
   m.def("mfma_test_32x32x16", &mfma_test_32x32x16, "MFMA 32x32x16 layout validation");
+  m.def("attn_tile_test_roundtrip", &attn_tile_test_roundtrip,
+        "attn_tile.h staging: int16 [64,128] -> (normal, transposed) LDS images read back");
+  m.def("attn_tile_test_pack_pair", &attn_tile_test_pack_pair,
+        "attn_tile.h pack_pair: fp32 [32,32] in C layout -> int32 [64,2,4] A-fragment words");
+  m.def("attn_tile_test_pack_frag16", &attn_tile_test_pack_frag16,
+        "attn_tile.h pack_frag16: fp32 [32,16] in C layout -> int32 [64,4] A-fragment words");
 }

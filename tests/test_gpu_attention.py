@@ -90,7 +90,7 @@ def test_attention_fwd_gqa(ext):
 
 
 def test_attention_fwd_odd_seq(ext):
-    """S not a multiple of the 128-row workgroup tile."""
+    """S not a multiple of the 256-row workgroup tile."""
     torch.manual_seed(3)
     B, S, H, D = 1, 200, 2, 128
     q = torch.randn(B, S, H, D, device=_dev(), dtype=torch.bfloat16)
