@@ -176,6 +176,18 @@ class GatherKVCache:
             return self.parent.lengths[lo:hi]
         return self.parent.lengths[self.slots]
 
+    @property
+    def rows(self) -> torch.Tensor:
+        """Parent-cache row of every active slot (memoised): what the fused
+        decode kernel indexes the parent tensors with."""
+        if getattr(self, "_rows", None) is None:
+            if self.range is not None:
+                lo, hi = self.range
+                self._rows = torch.arange(lo, hi, device=self.parent.lengths.device)
+            else:
+                self._rows = self.slots
+        return self._rows
+
     def append_one(self, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
         """Scatter single-token K/V ([N,1,Hkv,D]) at each active row's own
         length; returns the new per-row lengths."""
@@ -222,6 +234,19 @@ class LlamaAttention(nn.Module):
             # attention masked by per-row key validity.
             assert S == 1, "ragged cache is a single-token decode contract"
             tick = getattr(cache, "tick", None)  # per-tick hoisted tensors
+            if ops.decode_attention_hip_supported(q, self.num_kv_heads):
+                # fused kernel on the parent cache tensors: RoPE, cache
+                # write and GQA attention in one launch - no gather, no
+                # repeat_interleave, no mask
+                parent = getattr(cache, "parent", cache)
+                pos = getattr(tick, "pos", None)
+                o = ops.decode_attention(
+                    q, k, v, parent.k, parent.v, cos, sin,
+                    pos if pos is not None else cache.lengths,
+                    rows=cache.rows if parent is not cache else None,
+                    lengths=parent.lengths,
+                    max_len=getattr(cache, "total_hint", None))
+                return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
             if tick is not None:
                 q = ops.apply_rope_cs(q, tick.cos, tick.sin)
                 k = ops.apply_rope_cs(k, tick.cos, tick.sin)
@@ -253,6 +278,14 @@ class LlamaAttention(nn.Module):
             ).transpose(1, 2).contiguous()
             return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
         pos = cache.length if cache is not None else 0
+        if (S == 1 and pos > 0 and isinstance(cache, KVCache)
+                and ops.decode_attention_hip_supported(q, self.num_kv_heads)):
+            # uniform single-token decode: the same fused kernel, every row
+            # at position `pos`
+            o = ops.decode_attention(q, k, v, cache.k, cache.v, cos, sin, pos,
+                                     max_len=pos + 1)
+            cache.length = pos + 1
+            return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
         q = ops.apply_rope(q, cos, sin, pos_offset=pos)
         k = ops.apply_rope(k, cos, sin, pos_offset=pos)
         if cache is None:

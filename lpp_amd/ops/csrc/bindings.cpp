@@ -26,6 +26,13 @@ std::vector<double> attention_time_kernel(std::string kernel, at::Tensor dO, at:
                                           at::Tensor k, at::Tensor v, at::Tensor o,
                                           at::Tensor lse2, int64_t mode, int64_t G,
                                           int64_t warmup, int64_t reps);
+at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
+                            at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
+                            at::Tensor sin_t, c10::optional<at::Tensor> positions,
+                            c10::optional<at::Tensor> rows,
+                            c10::optional<at::Tensor> lengths, int64_t uniform_pos,
+                            int64_t max_len, int64_t chunk);
+int64_t attention_decode_chunk();
 at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B);
 void wgrad_f32_accum(at::Tensor x, at::Tensor dy, at::Tensor dw);
 void wgrad_f32_accum_pre(at::Tensor xT, at::Tensor dyT, at::Tensor dw);
@@ -74,6 +81,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "block order", py::arg("kernel"), py::arg("dO"), py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("o"), py::arg("lse2"), py::arg("mode"), py::arg("G") = 0,
         py::arg("warmup") = 3, py::arg("reps") = 20);
+  m.def("attention_decode", &attention_decode,
+        "fused single-token decode: RoPE + KV-cache write + GQA attention over keys 0..p of "
+        "each row's cache row -> o [N,1,H,128]; chunk 0 = the compiled-in chunk size",
+        py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("cos"), py::arg("sin"), py::arg("positions"),
+        py::arg("rows"), py::arg("lengths"), py::arg("uniform_pos"), py::arg("max_len"),
+        py::arg("chunk") = 0);
+  m.def("attention_decode_chunk", &attention_decode_chunk,
+        "keys per workgroup of attention_decode");
   m.def("wgrad_f32_accum", &wgrad_f32_accum, "dW_f32 += dY^T @ X (hipBLASLt, beta=1)");
   m.def("wgrad_f32_accum_pre", &wgrad_f32_accum_pre,
         "dW_f32 += dyT @ xT^T, pre-transposed k-contiguous operands (hipBLASLt, beta=1)");

@@ -6,9 +6,10 @@ and then decodes in ONE batched single-token step per engine tick together
 with every other active request — finished requests retire and free their
 slot immediately, so short requests never wait for long ones (the
 "continuous"/in-flight batching of production serving stacks).  Decode
-attention is the ragged per-row-length branch of ``LlamaAttention``
-(eager SDPA: single-token decode is latency/memory-bound; a dedicated
-decode GEMV kernel is BACKLOG work).
+attention is the ragged per-row-length branch of ``LlamaAttention``: for
+bf16 / head_dim 128 one fused gfx950 kernel per layer (``ops.decode_attention``
+- RoPE, cache write and GQA attention over each row's own prefix, read
+straight from the slot cache), eager SDPA otherwise.
 
 The reference has no inference capability at all (training-only template,
 SURVEY.md §0); this extends the framework's own ``generate``/
@@ -200,6 +201,7 @@ class ContinuousBatchingEngine:
         tick.sin = sin[pos].view(len(slots), 1, 1, -1)
         tick.mask = (torch.arange(total, device=self.device)[None, :]
                      <= pos[:, None])[:, None, None, :]
+        tick.pos = pos  # the fused decode kernel gathers RoPE phases itself
         for v in self._views:
             v.total_hint = total
             v.tick = tick
