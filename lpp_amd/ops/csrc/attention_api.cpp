@@ -85,6 +85,37 @@ at::Tensor attention_block_order(int64_t kind, int64_t nblk, int64_t nheads, int
   return out;
 }
 
+// Host only: the 64 per-lane LDS byte addresses (within one image) of one access
+// the kernels issue, from the header functions they run (attn_tile.h).  shape =
+// 32 (32x32x16: forward, dQ) or 16 (16x16x32: dK/dV):
+//   "stage"  ds_write_b128 of wave idx>>1, pass idx&1                (idx < 16)
+//   "row"    ds_read_b128 A-fragment: shape 32 idx = t2*8 + dc       (idx < 16)
+//                                     shape 16 idx = rt*4 + dc       (idx < 16)
+//   "tr"     ds_read_b64_tr_b16, h = idx&1 of the two reads of a B-fragment:
+//            shape 32 idx = (dt*4 + ks)*2 + h, shape 16 idx = (dt*2 + half)*2 + h
+//                                                                    (idx < 32)
+at::Tensor attention_lds_addresses(std::string pattern, int64_t shape, int64_t idx) {
+  TORCH_CHECK(shape == 32 || shape == 16, "attention_lds_addresses: shape 32 or 16");
+  const bool stage = pattern == "stage", row = pattern == "row", tr = pattern == "tr";
+  TORCH_CHECK(stage || row || tr, "attention_lds_addresses: pattern is stage, row or tr");
+  TORCH_CHECK(idx >= 0 && idx < (tr ? 32 : 16), "attention_lds_addresses: idx out of range");
+  auto out = at::empty({64}, at::TensorOptions().dtype(at::kInt));
+  int* p = out.data_ptr<int>();
+  const int i = (int)idx;
+  for (int lane = 0; lane < 64; ++lane) {
+    if (stage)
+      p[lane] = shape == 32 ? lpp::attn_stage_off<32>(i >> 1, i & 1, lane)
+                            : lpp::attn_stage_off<16>(i >> 1, i & 1, lane);
+    else if (row)
+      p[lane] = shape == 32 ? lpp::attn_row_off32(lane, i >> 3, i & 7)
+                            : lpp::attn_row_off16(lane, i >> 2, i & 3);
+    else
+      p[lane] = shape == 32 ? lpp::attn_tr_off32(lane, i >> 3, (i >> 1) & 3, i & 1)
+                            : lpp::attn_tr_off16(lane, i >> 2, (i >> 1) & 1, i & 1);
+  }
+  return out;
+}
+
 // Device-timed A/B of one attention kernel under an explicit block order:
 // kernel "fwd" | "dq" | "dkdv", order (mode, G; G <= 0 = the computed group).
 // One hipEvent pair per launch; returns the ms of each of `reps` launches

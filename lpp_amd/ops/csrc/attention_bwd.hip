@@ -13,8 +13,9 @@
 // in registers (pack_pair / pack_frag16, attn_tile.h).  Both big kernels run
 // one 512-thread workgroup per CU (2 waves/SIMD) through the attn_tile_pipeline
 // schedule (dK/dV calls the template, dQ writes the same steps out):
-// double-buffered 64-row LDS tiles, normal images for the A-fragment reads
-// and transposed images for the B-fragment reads, one barrier per tile.  The
+// double-buffered 64-row LDS tiles, one dual-use image per staged operand
+// (attn_tile.h), read by rows (ds_read_b128) for the A-fragments and by columns
+// (ds_read_b64_tr_b16) for the B-fragments, one barrier per tile.  The
 // wave id is read into a scalar register, so the tile class (past the
 // diagonal / masked / interior) is a scalar branch; interior tiles run a
 // straight-line softmax, diagonal and tail tiles the masked form.
@@ -27,7 +28,7 @@
 //        S^T  = mfma(K_lds, Q_reg)   C[kv regs][q lane]
 //        dP^T = mfma(V_lds, dO_reg)  same layout
 //        P    = exp2(c*S^T - L[own q]);  dS = P*(dP^T - delta[own q])
-//        dQ  += mfma(pack_pair(dS), K^T image)     (scale at epilogue)
+//        dQ  += mfma(pack_pair(dS), K_lds transposed reads)  (scale at epilogue)
 //   3. dK/dV — 8 waves x 16 kv rows (lane&15 = own kv row, 16x16x32
 //      fragments), grid over 128-row kv blocks x B*HKV; per 64-row q tile,
 //      run as two 32-row halves:
@@ -35,8 +36,8 @@
 //        dP   = mfma(dO_lds, V_reg)  same layout
 //        P    = exp2(c*S - L[q]);  dS = P*(dP - delta[q])
 //                                    (L, delta read from a staged tile)
-//        dV  += mfma(pack_frag16(P),  dO^T image)
-//        dK  += mfma(pack_frag16(dS), Q^T image)   (scale at epilogue)
+//        dV  += mfma(pack_frag16(P),  dO_lds transposed reads)
+//        dK  += mfma(pack_frag16(dS), Q_lds transposed reads)  (scale at epilogue)
 //      GQA: the G query heads sharing a kv head accumulate in-register.
 #include "attention.h"
 
@@ -69,12 +70,13 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// dQ.  LDS images (96 KB): K and V normal, K^T transposed.
+// dQ.  LDS images (64 KB, attn_off<32>): K (row reads for S^T, transposed reads
+// for dQ) and V (row reads).
 constexpr int DQ_QW = 32, DQ_QB = 256, DQ_KVB = ATTN_TILE_ROWS;
-enum { DQ_K, DQ_V, DQ_KT, DQ_IMAGES };
+enum { DQ_K, DQ_V, DQ_IMAGES };
 constexpr int DQ_LDS_BYTES = attn_lds_bytes(DQ_IMAGES);
 
-// gfx950 (hipcc -O3): NumVgprs 254, ScratchSize 0, Occupancy 2 waves/SIMD.
+// gfx950 (hipcc -O3): NumVgprs 232, ScratchSize 0, Occupancy 2 waves/SIMD.
 // 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
 __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
@@ -86,7 +88,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto k_lds = [&](int buf) -> char* { return attn_img(smem, DQ_K, buf); };
   auto v_lds = [&](int buf) -> char* { return attn_img(smem, DQ_V, buf); };
-  auto kt_lds = [&](int buf) -> char* { return attn_img(smem, DQ_KT, buf); };
 
   const int tid = threadIdx.x;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar
@@ -123,6 +124,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
 
   const int st_r = lane >> 4;
   const int st_c = 8 * (lane & 15);
+  const int st_off[2] = {attn_stage_off<32>(wid, 0, lane), attn_stage_off<32>(wid, 1, lane)};
   const int kv_end = min(S, (qblk + 1) * DQ_QB);
 
   auto ld_tile = [&](int kv0, int pass, bf16x8& kreg, bf16x8& vreg) {
@@ -132,10 +134,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
     vreg = *reinterpret_cast<const bf16x8*>(&V[rb]);
   };
   auto write_tile = [&](int buf, int pass, bf16x8 kreg, bf16x8 vreg) {
-    const int r = stage_row(wid, pass, st_r);
-    stage_normal(k_lds(buf), r, st_c, kreg);
-    stage_normal(v_lds(buf), r, st_c, vreg);
-    stage_transposed(kt_lds(buf), r, st_c, st_r, kreg);
+    stage_chunk(k_lds(buf), st_off[pass], kreg);
+    stage_chunk(v_lds(buf), st_off[pass], vreg);
   };
 
   f32x16 dq_acc[4];
@@ -145,7 +145,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
     for (int r = 0; r < 16; ++r) dq_acc[dt][r] = 0.f;
 
   // attn_tile_pipeline (attn_tile.h) written out: passing this body to the
-  // template costs 57 more v_mov_b32 at 254 VGPRs and measured 3-5% slower.
+  // template cost 57 more v_mov_b32 and measured 3-5% slower (round 5, at 254
+  // VGPRs).
   bf16x8 kreg0, kreg1, vreg0, vreg1;
   ld_tile(0, 0, kreg0, vreg0);
   ld_tile(0, 1, kreg1, vreg1);
@@ -180,10 +181,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
         __builtin_amdgcn_s_setprio(1);  // favour the MFMA cluster (guide T5)
 #pragma unroll
         for (int dc = 0; dc < 8; ++dc) {
-          const bf16x8 ak = *reinterpret_cast<const bf16x8*>(
-              k_lds(cur) + rswz(t2 * 32 + lq, dc * 16 + hi2 * 8));
-          const bf16x8 av = *reinterpret_cast<const bf16x8*>(
-              v_lds(cur) + rswz(t2 * 32 + lq, dc * 16 + hi2 * 8));
+          const bf16x8 ak = read_row_frag(k_lds(cur), attn_row_off32(lane, t2, dc));
+          const bf16x8 av = read_row_frag(v_lds(cur), attn_row_off32(lane, t2, dc));
           st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, qf[dc], st, 0, 0, 0);
           dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, dof[dc], dpt, 0, 0, 0);
         }
@@ -210,11 +209,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          const int d = dt * 32 + lq;
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
-            const bf16x8 bk = *reinterpret_cast<const bf16x8*>(
-                kt_lds(cur) + tswz(d, (2 * t2 + ks) * 16 + hi2 * 8));
+            const bf16x8 bk =
+                read_tr_frag(k_lds(cur), attn_tr_off32(lane, dt, 2 * t2 + ks, 0),
+                             attn_tr_off32(lane, dt, 2 * t2 + ks, 1));
             dq_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[ks], bk, dq_acc[dt], 0, 0, 0);
           }
         }
@@ -236,15 +235,16 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// dK/dV.  LDS images (128 KB): Q and dO normal, Q^T and dO^T transposed; then
-// the tile's 64 LSE2 and 64 delta values, double-buffered like the images.
+// dK/dV.  LDS images (64 KB, attn_off<16>): Q and dO, each read by rows for S
+// and dP and by transposed reads for dK and dV; then the tile's 64 LSE2 and 64
+// delta values, double-buffered like the images.
 constexpr int KV_KW = 16, KV_WG = 128, KV_QT = ATTN_TILE_ROWS;
-enum { KV_Q, KV_DO, KV_QTR, KV_DOTR, KV_IMAGES };
+enum { KV_Q, KV_DO, KV_IMAGES };
 constexpr int KV_LD_OFF = attn_lds_bytes(KV_IMAGES);                   // float L[2][64]
 constexpr int KV_D_OFF = KV_LD_OFF + 2 * KV_QT * (int)sizeof(float);   // float D[2][64]
 constexpr int KV_LDS_BYTES = KV_D_OFF + 2 * KV_QT * (int)sizeof(float);
 
-// gfx950 (hipcc -O3): NumVgprs 220, ScratchSize 0, Occupancy 2 waves/SIMD.
+// gfx950 (hipcc -O3): NumVgprs 210, ScratchSize 0, Occupancy 2 waves/SIMD.
 // 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
 __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
@@ -256,8 +256,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto q_lds = [&](int buf) -> char* { return attn_img(smem, KV_Q, buf); };
   auto do_lds = [&](int buf) -> char* { return attn_img(smem, KV_DO, buf); };
-  auto qt_lds = [&](int buf) -> char* { return attn_img(smem, KV_QTR, buf); };
-  auto dot_lds = [&](int buf) -> char* { return attn_img(smem, KV_DOTR, buf); };
   auto l_buf = [&](int buf) -> float* {
     return reinterpret_cast<float*>(smem + KV_LD_OFF) + buf * KV_QT; };
   auto d_buf = [&](int buf) -> float* {
@@ -301,6 +299,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
 
   const int st_r = (lane >> 4) & 3;
   const int st_c = 8 * (lane & 15);
+  const int st_off[2] = {attn_stage_off<16>(wid, 0, lane), attn_stage_off<16>(wid, 1, lane)};
   const int qstart = kvblk * KV_WG;
 
   for (int g = 0; g < G; ++g) {
@@ -315,11 +314,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
       dreg = *reinterpret_cast<const bf16x8*>(&dO[rb]);
     };
     auto write_tile = [&](int buf, int qt0, int pass, bf16x8 qreg, bf16x8 dreg) {
-      const int r = stage_row(wid, pass, st_r);
-      stage_normal(q_lds(buf), r, st_c, qreg);
-      stage_normal(do_lds(buf), r, st_c, dreg);
-      stage_transposed(qt_lds(buf), r, st_c, st_r, qreg);
-      stage_transposed(dot_lds(buf), r, st_c, st_r, dreg);
+      stage_chunk(q_lds(buf), st_off[pass], qreg);
+      stage_chunk(do_lds(buf), st_off[pass], dreg);
       if (pass == 0 && tid < 128) {
         const int qi = min(qt0 + (tid & 63), S - 1);
         if (tid < 64) l_buf(buf)[tid] = LSE2[ld_base + qi];
@@ -343,10 +339,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
         for (int dc = 0; dc < 4; ++dc) {
 #pragma unroll
           for (int qs = 0; qs < 2; ++qs) {
-            const bf16x8 aq = *reinterpret_cast<const bf16x8*>(
-                q_lds(cur) + rswz(half * 32 + qs * 16 + l16, dc * 32 + hi4 * 8));
-            const bf16x8 ad = *reinterpret_cast<const bf16x8*>(
-                do_lds(cur) + rswz(half * 32 + qs * 16 + l16, dc * 32 + hi4 * 8));
+            const int off = attn_row_off16(lane, 2 * half + qs, dc);
+            const bf16x8 aq = read_row_frag(q_lds(cur), off);
+            const bf16x8 ad = read_row_frag(do_lds(cur), off);
             st[qs] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq, kf[dc], st[qs], 0, 0, 0);
             dpt[qs] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ad, vf[dc], dpt[qs], 0, 0, 0);
           }
@@ -387,11 +382,10 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) {
-          const int d = dt * 16 + l16;
-          const bf16x8 bd = *reinterpret_cast<const bf16x8*>(
-              dot_lds(cur) + tswz(d, half * 32 + hi4 * 8));
-          const bf16x8 bq = *reinterpret_cast<const bf16x8*>(
-              qt_lds(cur) + tswz(d, half * 32 + hi4 * 8));
+          const int off0 = attn_tr_off16(lane, dt, half, 0);
+          const int off1 = attn_tr_off16(lane, dt, half, 1);
+          const bf16x8 bd = read_tr_frag(do_lds(cur), off0, off1);
+          const bf16x8 bq = read_tr_frag(q_lds(cur), off0, off1);
           dv_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, bd, dv_acc[dt], 0, 0, 0);
           dk_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsa, bq, dk_acc[dt], 0, 0, 0);
         }

@@ -14,10 +14,10 @@
 //     with the partner lane), no ds_bpermute chains
 //   - P -> PV A-fragments via v_cvt_pk_bf16_f32 + permlane32_swap pairs
 //     (pack_pair)
-//   - K tile [64][128] in LDS as a normal (rswz) image; V tile stored
-//     TRANSPOSED [128][64] (tswz image): the PV B-fragment read is 8
-//     contiguous bf16, ~conflict-free; the transpose itself is done
-//     in-register (quad_transpose) so the LDS writes are vectorised b64
+//   - K and V tiles [64][128] in LDS as one dual-use image each
+//     (attn_off<32>): K is read by rows (ds_read_b128) for S^T, V by columns
+//     with the transposing ds_read_b64_tr_b16 for the PV B-fragments, both
+//     conflict-free; staging is one ds_write_b128 per row-slice and image
 //   - double-buffered LDS, one barrier per KV tile; next tile's global
 //     loads issued before the compute phase (attn_tile_pipeline)
 //   - defer-max online softmax (AF_THR = 8): the O rescale (and
@@ -36,7 +36,7 @@ constexpr int AF_QW = 32;      // q rows per wave
 constexpr int AF_QB = 256;     // q rows per workgroup (8 waves)
 constexpr int AF_KVB = ATTN_TILE_ROWS;  // kv tile rows
 constexpr float AF_THR = 8.0f; // defer-max threshold (exp2 domain)
-enum { AF_K, AF_VT, AF_IMAGES };  // LDS images: K normal, V transposed
+enum { AF_K, AF_V, AF_IMAGES };  // LDS images (64 KB): K, V
 constexpr int AF_LDS_BYTES = attn_lds_bytes(AF_IMAGES);
 
 // 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
@@ -47,10 +47,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto k_lds = [&](int buf) -> char* { return attn_img(smem, AF_K, buf); };
-  auto vt_lds = [&](int buf) -> char* { return attn_img(smem, AF_VT, buf); };
+  auto v_lds = [&](int buf) -> char* { return attn_img(smem, AF_V, buf); };
 
   const int tid = threadIdx.x;
-  const int wid = tid >> 6;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar
   const int lane = tid & 63;
   const int lq = lane & 31;        // this lane's q row (within the wave)
   const int hi2 = lane >> 5;
@@ -83,6 +83,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
   // ---- staging (per thread and pass: one K row-slice + one V row-slice) ----
   const int st_r = (lane >> 4);            // 0..3 within the wave's 4 rows
   const int st_c = 8 * (lane & 15);        // 0..120
+  const int st_off[2] = {attn_stage_off<32>(wid, 0, lane), attn_stage_off<32>(wid, 1, lane)};
 
   const int kv_end = min(S, (qblk + 1) * AF_QB);
 
@@ -93,9 +94,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     vreg = *reinterpret_cast<const bf16x8*>(&V[rb]);
   };
   auto write_tile = [&](int buf, int /*kv0*/, int pass, bf16x8 kreg, bf16x8 vreg) {
-    const int r = stage_row(wid, pass, st_r);  // row within [0,64)
-    stage_normal(k_lds(buf), r, st_c, kreg);
-    stage_transposed(vt_lds(buf), r, st_c, st_r, vreg);
+    stage_chunk(k_lds(buf), st_off[pass], kreg);
+    stage_chunk(v_lds(buf), st_off[pass], vreg);
   };
 
   // ---- accumulators & softmax state ----
@@ -107,7 +107,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
   float m_run = -INFINITY, l_run = 0.f;
 
   attn_tile_pipeline<AF_KVB>(0, kv_end, ld_tile, write_tile, [&](int kv0, int cur) {
-    if (kv0 >= qw0 + AF_QW) return;  // causal: this wave has no work in this tile
+    // causal: this wave has no work in this tile (a scalar branch: the
+    // transposed reads below need every lane active)
+    if (kv0 >= qw0 + AF_QW) return;
     // ---- S^T = K Q^T: two 32x32 tiles over kv ----
     f32x16 st[2];
 #pragma unroll
@@ -119,8 +121,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     for (int dc = 0; dc < 8; ++dc) {
 #pragma unroll
       for (int t2 = 0; t2 < 2; ++t2) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(
-            k_lds(cur) + rswz(t2 * 32 + lq, dc * 16 + hi2 * 8));
+        const bf16x8 kf = read_row_frag(k_lds(cur), attn_row_off32(lane, t2, dc));
         st[t2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[dc], st[t2], 0, 0, 0);
       }
     }
@@ -188,15 +189,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     pack_pair(&p[0], &pa[0]);
     pack_pair(&p[16], &pa[2]);
 
-    // ---- O += P V  (B-frags from the transposed V image) ----
+    // ---- O += P V  (B-frags: transposed reads of the V image) ----
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
-      const int d = dt * 32 + lq;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const bf16x8 bv = *reinterpret_cast<const bf16x8*>(
-            vt_lds(cur) + tswz(d, ks * 16 + hi2 * 8));
+        const bf16x8 bv = read_tr_frag(v_lds(cur), attn_tr_off32(lane, dt, ks, 0),
+                                       attn_tr_off32(lane, dt, ks, 1));
         o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[ks], bv, o_acc[dt], 0, 0, 0);
       }
     }
@@ -219,7 +219,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     LSE2[((int64_t)b * H + h) * S + qrow] = m_run + log2f(l_run);
 }
 
-// 231 VGPRs, 2 waves/SIMD; order_G: see attention.h.
+// gfx950 (hipcc -O3): NumVgprs 207, ScratchSize 0, 2 waves/SIMD, 64 KB LDS.
+// order_G: see attention.h.
 void launch_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                      at::Tensor& o, at::Tensor& lse2, int order_mode, int order_G) {
   const int B = q.size(0), S = q.size(1), H = q.size(2);

@@ -1,8 +1,9 @@
 // Device helpers shared by the three attention kernels (attention_fwd.hip,
 // attention_bwd.hip) and exercised on their own by the test kernels in
-// mfma_test.hip (tests/test_gpu_attention_tile.py): vector types, the two LDS
-// image layouts, register-file fragment packs, tile staging and the
-// double-buffered tile pipeline.
+// mfma_test.hip (tests/test_gpu_attention_tile.py,
+// tests/test_gpu_attention_tr_image.py): vector types, the dual-use LDS image
+// layout with its staging, row-read and transposed-read addresses,
+// register-file fragment packs and the double-buffered tile pipeline.
 #pragma once
 
 #include "common.h"
@@ -10,13 +11,14 @@
 namespace lpp {
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
+typedef __attribute__((ext_vector_type(4))) short bf16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) int int2v;
 
 constexpr int ATTN_D = 128;        // head dim
 constexpr int ATTN_TILE_ROWS = 64; // rows of one staged tile
-// One LDS image, normal [64][128] or transposed [128][64], bf16.
+// One LDS image, [64][128] bf16.
 constexpr int ATTN_IMG_BYTES = ATTN_TILE_ROWS * ATTN_D * 2;
 
 // Image `slot` of a kernel's dynamic LDS; every image is double-buffered, so a
@@ -49,74 +51,112 @@ __device__ __forceinline__ int crow32(int r, int hi2) {
   return (r & 3) + 8 * (r >> 2) + 4 * hi2;
 }
 
-// ---- LDS image layouts -------------------------------------------------------
-// Normal image [rows][128] bf16, row stride 256 B, byte offset XORed with
-// (row&15)<<4: the 16-lane ds_read_b128 A-fragment groups are conflict-free.
-__device__ __forceinline__ int rswz(int row, int col_elem) {
-  return row * 256 + ((col_elem * 2) ^ ((row & 15) << 4));
-}
-// Transposed image [128 d][64 r] bf16; byte offset of element (d, r) =
-// (d*64 + (r ^ ((((d>>3) ^ d) & 7) << 3))) * 2.  Writes are ~2-way (the XOR
-// varies with the lane's d), B-fragment reads conflict-free (measured 0.9%
-// conflict cycles in the forward vs 8-15% for padded strides).
-__device__ __forceinline__ int tswz(int d, int r) {
-  return (d * 64 + (r ^ ((((d >> 3) ^ d) & 7) << 3))) * 2;
-}
+// ---- LDS image layout ---------------------------------------------------------
+// One image [64][128] bf16 with 256-byte rows serves BOTH kinds of fragment
+// read: the row reads (ds_read_b128, A operands) and the column reads of the
+// B operands, taken with the transposing ds_read_b64_tr_b16, so no tile is kept
+// a second time in transposed form.  attn_off<M>(row, ch) is the byte offset of
+// 16-byte chunk ch (0..15) of a row; the chunk is XORed with a function of
+// row & 15 that depends on the MFMA shape M whose operands are read from it:
+//   M = 32 (32x32x16: forward, dQ)  (row&3)<<2 | (row>>2)&3
+//   M = 16 (16x16x32: dK/dV)        f(r)=2r, f(4+r)=8+2r, f(8+r)=9+2r,
+//                                   f(12+r)=2r+1  (r = 0..3)
+// Every access pattern below is free of bank conflicts on its layout
+// (tests/test_attention_lds_layout.py runs a bank model over the addresses
+// bound as attention_lds_addresses).  All functions are evaluated on the host
+// as well, from this header.
+#define ATTN_HD __host__ __device__ __forceinline__
 
-// 4x4 dword butterfly across the lane quad {l, l^16, l^32, l^48}, each lane
-// holding 8 bf16 of one row at the same column c: the lane with quad position
-// p ends holding dword p of each quad row, out[i] = row i at columns c+2p, c+2p+1.
-__device__ __forceinline__ void quad_transpose(const bf16x8& v, int p, int out[4]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) out[k] = reinterpret_cast<const int*>(&v)[k];
-  {  // bit0 of dword index <-> bit0 of quad pos (xor 16)
-    int t0 = __shfl_xor(out[(p & 1) ^ 1], 16);
-    int t1 = __shfl_xor(out[((p & 1) ^ 1) | 2], 16);
-    if (p & 1) { out[0] = t0; out[2] = t1; } else { out[1] = t0; out[3] = t1; }
-  }
-  {  // bit1 of dword index <-> bit1 of quad pos (xor 32)
-    int lo = (p & 2) ? 0 : 2;
-    int t0 = __shfl_xor(out[lo], 32);
-    int t1 = __shfl_xor(out[lo + 1], 32);
-    out[lo] = t0; out[lo + 1] = t1;
-  }
+ATTN_HD int attn_swz32(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
+ATTN_HD int attn_swz16(int row) {
+  const int a = row & 3, b = (row >> 2) & 3;
+  return (a << 1) | (((b ^ (b >> 1)) & 1) << 3) | (b >> 1);
 }
-
-// Write the quad-transposed columns into a transposed image as 2x ds_write_b64;
-// r0 = quad's first row (multiple of 4), d0 = first column this lane owns.
-__device__ __forceinline__ void write_transposed(char* img, int r0, int d0,
-                                                 const int dw[4]) {
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int d = d0 + e;  // column e: bf16 of rows 0..3 = half e of dw[0..3]
-    unsigned w01 = e ? (((unsigned)dw[0] >> 16) | ((unsigned)dw[1] & 0xffff0000u))
-                     : (((unsigned)dw[0] & 0xffffu) | ((unsigned)dw[1] << 16));
-    unsigned w23 = e ? (((unsigned)dw[2] >> 16) | ((unsigned)dw[3] & 0xffff0000u))
-                     : (((unsigned)dw[2] & 0xffffu) | ((unsigned)dw[3] << 16));
-    int2v pair = {(int)w01, (int)w23};
-    *reinterpret_cast<int2v*>(img + tswz(d, r0)) = pair;
-  }
+template <int M>
+ATTN_HD int attn_off(int row, int ch) {
+  static_assert(M == 32 || M == 16, "MFMA shape: 32 (32x32x16) or 16 (16x16x32)");
+  return 256 * row + 16 * (ch ^ (M == 32 ? attn_swz32(row) : attn_swz16(row)));
 }
 
 // ---- staging -----------------------------------------------------------------
 // 512 threads stage one [64][128] tile in two passes of one 8-element row-slice
-// per thread: wave wid takes rows 4*wid .. 4*wid+3 (+32 in pass 1), lane l row
-// position p = l>>4 and column 8*(l&15), so each lane quad {l, l^16, l^32, l^48}
-// holds four consecutive rows at one column for the transpose butterfly.
-__device__ __forceinline__ int stage_row(int wid, int pass, int p) {
-  return 4 * wid + 32 * pass + p;
+// (one chunk, a ds_write_b128) per thread: wave wid takes rows 4*wid .. 4*wid+3
+// (+32 in pass 1), lane l row position l>>4 and chunk l&15.
+ATTN_HD int stage_row(int wid, int pass, int p) { return 4 * wid + 32 * pass + p; }
+template <int M>
+ATTN_HD int attn_stage_off(int wid, int pass, int lane) {
+  return attn_off<M>(stage_row(wid, pass, lane >> 4), lane & 15);
 }
-// One row-slice (row r, columns c..c+7) into a normal image: a b128 write.
-__device__ __forceinline__ void stage_normal(char* img, int r, int c, const bf16x8& v) {
-  *reinterpret_cast<bf16x8*>(img + rswz(r, c)) = v;
+
+// ---- fragment addresses --------------------------------------------------------
+// Each read's offset is (base ^ column term) + row term: a per-lane base, taken
+// from attn_off at the fragment's first position, XORed with a compile-time
+// column term (the swizzle is an XOR and the base keeps those bits clear of the
+// row part) plus a compile-time row term for the instruction's offset field
+// (the swizzles repeat every 16 rows).  A kernel short of registers keeps the
+// one base and recomputes the XOR per read (dQ).
+//
+// Row reads (A operands), one ds_read_b128:
+//   32x32x16  A[m = lane&31][k = (lane>>5)*8 + j] = tile[t2*32 + m][dc*16 + k]
+//   16x16x32  A[m = lane&15][k = (lane>>4)*8 + j] = tile[rt*16 + m][dc*32 + k]
+ATTN_HD int attn_row_base32(int lane) { return attn_off<32>(lane & 31, lane >> 5); }
+ATTN_HD int attn_row_at32(int base, int t2, int dc) {
+  return (base ^ (32 * dc)) + 32 * 256 * t2;
 }
-// The quad's four row-slices into a transposed image; every lane of the quad
-// calls this with its own row r = r0 + p.
-__device__ __forceinline__ void stage_transposed(char* img, int r, int c, int p,
-                                                 const bf16x8& v) {
-  int dw[4];
-  quad_transpose(v, p, dw);
-  write_transposed(img, r - p, c + 2 * p, dw);
+ATTN_HD int attn_row_off32(int lane, int t2, int dc) {
+  return attn_row_at32(attn_row_base32(lane), t2, dc);
+}
+ATTN_HD int attn_row_base16(int lane) { return attn_off<16>(lane & 15, lane >> 4); }
+ATTN_HD int attn_row_at16(int base, int rt, int dc) {
+  return (base ^ (64 * dc)) + 16 * 256 * rt;
+}
+ATTN_HD int attn_row_off16(int lane, int rt, int dc) {
+  return attn_row_at16(attn_row_base16(lane), rt, dc);
+}
+// Transposed reads (B operands), two ds_read_b64_tr_b16 (h = 0, 1) of four rows
+// each.  In a 16-lane group, lane 4q+p supplies the address of row q, columns
+// 4p..4p+3 of a 4-row x 16-column block, and lane i receives column i with row
+// q in element q; the two reads fill k = hi*8 + j, j = 4h .. 4h+3:
+//   32x32x16  B[k = (lane>>5)*8 + j][n = lane&31] = tile[ks*16 + k][dt*32 + n]
+//   16x16x32  B[k = (lane>>4)*8 + j][n = lane&15] = tile[half*32 + k][dt*16 + n]
+// Rows 4h+q of an 8-row group differ from rows q in one swizzle bit: chunk bit 0
+// (M = 32) or chunk bit 3 (M = 16).
+ATTN_HD int attn_tr_base32(int lane) {
+  const int q = (lane >> 2) & 3, p = lane & 3;
+  return attn_off<32>((lane >> 5) * 8 + q, 2 * ((lane >> 4) & 1) + (p >> 1)) + 8 * (p & 1);
+}
+ATTN_HD int attn_tr_at32(int base, int dt, int ks, int h) {
+  return (base ^ (64 * dt + 16 * h)) + 4 * 256 * h + 16 * 256 * ks;
+}
+ATTN_HD int attn_tr_off32(int lane, int dt, int ks, int h) {
+  return attn_tr_at32(attn_tr_base32(lane), dt, ks, h);
+}
+ATTN_HD int attn_tr_base16(int lane) {
+  const int q = (lane >> 2) & 3, p = lane & 3;
+  return attn_off<16>((lane >> 4) * 8 + q, p >> 1) + 8 * (p & 1);
+}
+ATTN_HD int attn_tr_at16(int base, int dt, int half, int h) {
+  return (base ^ (32 * dt) ^ (128 * h)) + 4 * 256 * h + 32 * 256 * half;
+}
+ATTN_HD int attn_tr_off16(int lane, int dt, int half, int h) {
+  return attn_tr_at16(attn_tr_base16(lane), dt, half, h);
+}
+
+// ---- LDS accesses --------------------------------------------------------------
+// One row-slice (a 16-byte chunk) into an image at a staging offset.
+__device__ __forceinline__ void stage_chunk(char* img, int off, const bf16x8& v) {
+  *reinterpret_cast<bf16x8*>(img + off) = v;
+}
+__device__ __forceinline__ bf16x8 read_row_frag(const char* img, int off) {
+  return *reinterpret_cast<const bf16x8*>(img + off);
+}
+// ds_read_b64_tr_b16 needs EXEC all ones: call this under wave-uniform control
+// flow only (the wave id is a scalar in every kernel, tiles are always full).
+__device__ __forceinline__ bf16x8 read_tr_frag(const char* img, int off0, int off1) {
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(img + off0));
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(img + off1));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // ---- fragment packs (registers only, no LDS) ----------------------------------

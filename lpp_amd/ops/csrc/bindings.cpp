@@ -22,6 +22,7 @@ void attention_set_block_order(int64_t mode);
 int64_t attention_get_block_order();
 at::Tensor attention_block_order(int64_t kind, int64_t nblk, int64_t nheads, int64_t G,
                                  int64_t mode);
+at::Tensor attention_lds_addresses(std::string pattern, int64_t shape, int64_t idx);
 std::vector<double> attention_time_kernel(std::string kernel, at::Tensor dO, at::Tensor q,
                                           at::Tensor k, at::Tensor v, at::Tensor o,
                                           at::Tensor lse2, int64_t mode, int64_t G,
@@ -48,6 +49,8 @@ std::tuple<int64_t, std::string> wgrad_current_algo(int64_t T, int64_t in, int64
                                                     int64_t kind);
 at::Tensor mfma_test_32x32x16(at::Tensor A, at::Tensor B);
 std::vector<at::Tensor> attn_tile_test_roundtrip(at::Tensor tile);
+at::Tensor attn_tile_test_tr_fragments(at::Tensor tile, int64_t shape, int64_t nrows,
+                                       int64_t buf);
 at::Tensor attn_tile_test_pack_pair(at::Tensor x);
 at::Tensor attn_tile_test_pack_frag16(at::Tensor x);
 void fused_adamw(std::vector<at::Tensor> params, std::vector<at::Tensor> masters,
@@ -108,7 +111,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_test_16x16x32", &mfma_test_16x16x32, "MFMA layout validation");
   m.def("mfma_test_32x32x16", &mfma_test_32x32x16, "MFMA 32x32x16 layout validation");
   m.def("attn_tile_test_roundtrip", &attn_tile_test_roundtrip,
-        "attn_tile.h staging: int16 [64,128] -> (normal, transposed) LDS images read back");
+        "attn_tile.h dual-use image: int16 [64,128] -> (tile by row reads, transpose by "
+        "transposed reads) from one LDS image");
+  m.def("attn_tile_test_tr_fragments", &attn_tile_test_tr_fragments,
+        "attn_tile.h transposed reads: int16 [64,128] -> int16 [16,64,8], the B-fragments "
+        "of MFMA shape 32 (frag = dt*4+ks) or 16 (frag = dt*2+half) as the kernels read them",
+        py::arg("tile"), py::arg("shape"), py::arg("nrows") = 64, py::arg("buf") = 0);
+  m.def("attention_lds_addresses", &attention_lds_addresses,
+        "host: int32 [64] per-lane LDS byte addresses of one access pattern (stage | row | "
+        "tr) of MFMA shape 32 or 16", py::arg("pattern"), py::arg("shape"), py::arg("idx"));
   m.def("attn_tile_test_pack_pair", &attn_tile_test_pack_pair,
         "attn_tile.h pack_pair: fp32 [32,32] in C layout -> int32 [64,2,4] A-fragment words");
   m.def("attn_tile_test_pack_frag16", &attn_tile_test_pack_frag16,

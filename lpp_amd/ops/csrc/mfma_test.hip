@@ -63,28 +63,73 @@ __global__ void mfma_32x32x16_kernel(const __hip_bfloat16* __restrict__ A,
 }
 
 // ---- attn_tile.h helpers (tests/test_gpu_attention_tile.py) -------------------
-// One 512-thread workgroup stages a [64][128] tile into a normal and a
-// transposed image with the kernels' row assignment, then reads both back
-// element by element through the swizzle functions.
+// The 512 threads stage rows min(r, nrows - 1), r = 0..63, of `in` into image
+// 0 of buffer buf with the kernels' row assignment (the kernels clamp their
+// loads the same way, so a tile is always full).
+template <int M>
+__device__ __forceinline__ void test_stage_tile(char* smem, int buf, const short* in,
+                                                int nrows) {
+  const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int r = min(stage_row(wid, pass, lane >> 4), nrows - 1);
+    const bf16x8 v = *reinterpret_cast<const bf16x8*>(&in[r * ATTN_D + 8 * (lane & 15)]);
+    stage_chunk(attn_img(smem, 0, buf), attn_stage_off<M>(wid, pass, lane), v);
+  }
+  __syncthreads();
+}
+
+// One 512-thread workgroup stages a [64][128] tile into ONE dual-use image,
+// then returns the tile through the forward's row reads and its transpose
+// through the forward's transposed reads (32x32x16 operand maps).
 __global__ __launch_bounds__(512) void attn_tile_roundtrip_kernel(
     const short* __restrict__ in, short* __restrict__ out_n, short* __restrict__ out_t) {
   __shared__ __attribute__((aligned(16))) char smem[2 * ATTN_IMG_BYTES];
-  char* img_n = smem;
-  char* img_t = smem + ATTN_IMG_BYTES;
-  const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
-  const int st_r = lane >> 4, st_c = 8 * (lane & 15);
+  test_stage_tile<32>(smem, 0, in, ATTN_TILE_ROWS);
+  const char* img = attn_img(smem, 0, 0);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  // A-fragments (t2, dc): tile[t2*32 + lane&31][dc*16 + (lane>>5)*8 + j]
 #pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    const int r = stage_row(wid, pass, st_r);
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(&in[r * ATTN_D + st_c]);
-    stage_normal(img_n, r, st_c, v);
-    stage_transposed(img_t, r, st_c, st_r, v);
+  for (int f = 0; f < 2; ++f) {
+    const int t2 = wid >> 2, dc = 2 * (wid & 3) + f;
+    const bf16x8 a = read_row_frag(img, attn_row_off32(lane, t2, dc));
+    *reinterpret_cast<bf16x8*>(
+        &out_n[(t2 * 32 + (lane & 31)) * ATTN_D + dc * 16 + (lane >> 5) * 8]) = a;
   }
-  __syncthreads();
-  for (int i = tid; i < ATTN_TILE_ROWS * ATTN_D; i += 512) {
-    out_n[i] = *reinterpret_cast<const short*>(img_n + rswz(i / ATTN_D, i % ATTN_D));
-    out_t[i] = *reinterpret_cast<const short*>(
-        img_t + tswz(i / ATTN_TILE_ROWS, i % ATTN_TILE_ROWS));
+  // B-fragments (dt, ks): tile[ks*16 + (lane>>5)*8 + j][dt*32 + lane&31]
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int dt = wid >> 1, ks = 2 * (wid & 1) + f;
+    const bf16x8 b = read_tr_frag(img, attn_tr_off32(lane, dt, ks, 0),
+                                  attn_tr_off32(lane, dt, ks, 1));
+    *reinterpret_cast<bf16x8*>(
+        &out_t[(dt * 32 + (lane & 31)) * ATTN_TILE_ROWS + ks * 16 + (lane >> 5) * 8]) = b;
+  }
+}
+
+// The B-fragments exactly as the kernels read them, out[frag][lane][8]:
+//   M = 32 (forward, dQ): frag = dt*4 + ks,   dt = 0..3, ks = 0..3
+//   M = 16 (dK/dV):       frag = dt*2 + half, dt = 0..7, half = 0..1
+// staged into LDS buffer buf of a double-buffered image; each of the 8 waves
+// reads two of the 16 fragments.
+template <int M>
+__global__ __launch_bounds__(512) void attn_tr_fragments_kernel(
+    const short* __restrict__ in, short* __restrict__ out, int nrows, int buf) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * ATTN_IMG_BYTES];
+  test_stage_tile<M>(smem, buf, in, nrows);
+  const char* img = attn_img(smem, 0, buf);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int frag = 2 * wid + f;
+    bf16x8 b;
+    if (M == 32)
+      b = read_tr_frag(img, attn_tr_off32(lane, frag >> 2, frag & 3, 0),
+                       attn_tr_off32(lane, frag >> 2, frag & 3, 1));
+    else
+      b = read_tr_frag(img, attn_tr_off16(lane, frag >> 1, frag & 1, 0),
+                       attn_tr_off16(lane, frag >> 1, frag & 1, 1));
+    *reinterpret_cast<bf16x8*>(&out[(frag * 64 + lane) * 8]) = b;
   }
 }
 
@@ -148,7 +193,25 @@ at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B) {
   return C;
 }
 
-// [64,128] int16 -> (normal [64,128], transposed [128,64]) read back from LDS.
+// tile int16 [64,128] -> int16 [16,64,8]: the 16 B-fragments of MFMA shape
+// `shape` (32 | 16) read from LDS buffer `buf` (0 | 1), rows clamped to nrows.
+at::Tensor attn_tile_test_tr_fragments(at::Tensor tile, int64_t shape, int64_t nrows,
+                                       int64_t buf) {
+  TORCH_CHECK(tile.is_cuda() && tile.scalar_type() == at::kShort && tile.is_contiguous());
+  TORCH_CHECK(tile.sizes() == at::IntArrayRef({lpp::ATTN_TILE_ROWS, lpp::ATTN_D}));
+  TORCH_CHECK(shape == 32 || shape == 16, "attn_tile_test_tr_fragments: shape 32 or 16");
+  TORCH_CHECK(nrows >= 1 && nrows <= lpp::ATTN_TILE_ROWS && (buf == 0 || buf == 1));
+  auto out = at::zeros({16, 64, 8}, tile.options());
+  auto kernel = shape == 32 ? lpp::attn_tr_fragments_kernel<32>
+                            : lpp::attn_tr_fragments_kernel<16>;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(512), 0, lpp::current_stream(),
+                     tile.data_ptr<short>(), out.data_ptr<short>(), (int)nrows, (int)buf);
+  LPP_CHECK_HIP(hipGetLastError());
+  return out;
+}
+
+// [64,128] int16 -> (the tile [64,128], its transpose [128,64]), both read back
+// from one LDS image: by row reads and by transposed reads.
 std::vector<at::Tensor> attn_tile_test_roundtrip(at::Tensor tile) {
   TORCH_CHECK(tile.is_cuda() && tile.scalar_type() == at::kShort && tile.is_contiguous());
   TORCH_CHECK(tile.sizes() == at::IntArrayRef({lpp::ATTN_TILE_ROWS, lpp::ATTN_D}));

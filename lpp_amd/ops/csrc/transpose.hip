@@ -82,8 +82,9 @@ __global__ __launch_bounds__(256) void transpose2d_kernel(
 
 // ---------------------------------------------------------------------------
 // v2 (the shape-aligned fast path): 64-row x 128-col tiles through a
-// transposed XOR image (the attention kernels' 4x4 dword butterfly +
-// ((d>>3)^d)&7 block swizzle) — every LDS access is b64/b128 vectorised:
+// transposed XOR image (a 4x4 dword butterfly across lane quads + a
+// ((d>>3)^d)&7 block swizzle, the scheme the attention kernels used before
+// their transposing LDS reads) — every LDS access is b64/b128 vectorised:
 // load b128 -> in-register quad transpose -> 2x ds_write_b64 -> ds_read_b128
 // -> global b128 store.  v1 above stays for ragged shapes and fp16.
 
