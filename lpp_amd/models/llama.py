@@ -220,11 +220,17 @@ class LlamaAttention(nn.Module):
         self.v_proj = LPLinear(cfg.hidden_size, self.num_kv_heads * self.head_dim)
         self.o_proj = LPLinear(self.num_heads * self.head_dim, cfg.hidden_size)
 
-    def forward(self, x: torch.Tensor, cache: Optional["KVCache"] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, cache: Optional["KVCache"] = None,
+                x_k: Optional[torch.Tensor] = None,
+                x_v: Optional[torch.Tensor] = None) -> torch.Tensor:
+        # x_k / x_v: aliases of x for k_proj / v_proj (ops.rmsnorm_fork), so
+        # the three input gradients reach the norm backward unsummed
         B, S, _ = x.shape
         q = self.q_proj(x).view(B, S, self.num_heads, self.head_dim)
-        k = self.k_proj(x).view(B, S, self.num_kv_heads, self.head_dim)
-        v = self.v_proj(x).view(B, S, self.num_kv_heads, self.head_dim)
+        k = self.k_proj(x if x_k is None else x_k).view(
+            B, S, self.num_kv_heads, self.head_dim)
+        v = self.v_proj(x if x_v is None else x_v).view(
+            B, S, self.num_kv_heads, self.head_dim)
         cos, sin = ops.build_rope_cache(
             self.max_seq_len, self.head_dim, self.rope_theta, x.device
         )
@@ -327,8 +333,10 @@ class LlamaMLP(nn.Module):
         self.up_proj = LPLinear(cfg.hidden_size, cfg.intermediate_size)
         self.down_proj = LPLinear(cfg.intermediate_size, cfg.hidden_size)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.down_proj(ops.swiglu(self.gate_proj(x), self.up_proj(x)))
+    def forward(self, x: torch.Tensor, x_up: Optional[torch.Tensor] = None) -> torch.Tensor:
+        # x_up: alias of x for up_proj (ops.rmsnorm_fork)
+        return self.down_proj(ops.swiglu(
+            self.gate_proj(x), self.up_proj(x if x_up is None else x_up)))
 
 
 class DecoderLayerPipe(nn.Module):
@@ -349,8 +357,30 @@ class DecoderLayerPipe(nn.Module):
 
     def _forward_impl(self, hidden: torch.Tensor,
                       cache: Optional[KVCache] = None) -> torch.Tensor:
+        if cache is None and ops.rmsnorm_fork_applies(hidden) and (
+                hidden.requires_grad or self.input_layernorm.weight.requires_grad):
+            return self._forward_fork(hidden)
         hidden = hidden + self.self_attn(self.input_layernorm(hidden), cache=cache)
         hidden = hidden + self.mlp(self.post_attention_layernorm(hidden))
+        return hidden
+
+    def _forward_fork(self, hidden: torch.Tensor) -> torch.Tensor:
+        """GPU training path: same forward values, but each norm hands one
+        alias of its output to every consumer, so its backward receives the
+        partial gradients and the residual gradient unsummed and fuses the
+        adds (ops.rmsnorm_fork)."""
+        ln = self.input_layernorm
+        # The input gradient of this layer is a wgrad operand only if the
+        # layer before it is a decoder layer of the same graph (its
+        # down_proj); a stage's first layer needs no transposed image.
+        want_t = getattr(hidden, "_lpp_decoder_out", False)
+        hidden, xq, xk, xv = ops.rmsnorm_fork(
+            hidden, ln.weight, ln.variance_epsilon, 3, want_t)
+        hidden = hidden + self.self_attn(xq, x_k=xk, x_v=xv)
+        ln = self.post_attention_layernorm
+        hidden, xg, xu = ops.rmsnorm_fork(hidden, ln.weight, ln.variance_epsilon, 2, True)
+        hidden = hidden + self.mlp(xg, x_up=xu)
+        hidden._lpp_decoder_out = True
         return hidden
 
     def forward(self, hidden: torch.Tensor,

@@ -93,7 +93,7 @@ def use_hip(*tensors: torch.Tensor) -> bool:
     return True
 
 
-from .rmsnorm import rmsnorm  # noqa: E402
+from .rmsnorm import rmsnorm, rmsnorm_fork, rmsnorm_fork_applies  # noqa: E402
 from .rope import (build_rope_cache, apply_rope, apply_rope_positions,  # noqa: E402
                    apply_rope_cs)
 from .swiglu import swiglu  # noqa: E402
@@ -103,6 +103,8 @@ from .attention import (causal_attention, decode_attention,  # noqa: E402
 
 __all__ = [
     "rmsnorm",
+    "rmsnorm_fork",
+    "rmsnorm_fork_applies",
     "build_rope_cache",
     "apply_rope",
     "apply_rope_positions",

@@ -8,10 +8,16 @@
 std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor weight, double eps);
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor weight,
                                     at::Tensor invrms);
+std::vector<at::Tensor> rmsnorm_bwd_fused(std::vector<at::Tensor> dys, at::Tensor x,
+                                          at::Tensor weight, at::Tensor invrms,
+                                          c10::optional<at::Tensor> dres, bool want_t);
 at::Tensor rope_fwd(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, int64_t pos_offset);
 at::Tensor rope_bwd(at::Tensor dy, at::Tensor cos_t, at::Tensor sin_t, int64_t pos_offset);
+std::vector<at::Tensor> rope_bwd_t(at::Tensor dy, at::Tensor cos_t, at::Tensor sin_t,
+                                   int64_t pos_offset);
 at::Tensor swiglu_fwd(at::Tensor gate, at::Tensor up);
 std::vector<at::Tensor> swiglu_bwd(at::Tensor dy, at::Tensor gate, at::Tensor up);
+std::vector<at::Tensor> swiglu_bwd_t(at::Tensor dy, at::Tensor gate, at::Tensor up);
 std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits, at::Tensor labels);
 at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor labels, at::Tensor lse,
                              double scale);
@@ -63,10 +69,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "lpp_amd gfx950 (MI355X/CDNA4) kernels";
   m.def("rmsnorm_fwd", &rmsnorm_fwd, "RMSNorm forward (y, invrms)");
   m.def("rmsnorm_bwd", &rmsnorm_bwd, "RMSNorm backward (dx, dw)");
+  m.def("rmsnorm_bwd_fused", &rmsnorm_bwd_fused,
+        "RMSNorm backward with the gradient adds fused: sums 1..3 partial dy (bf16 rounding "
+        "after each add), adds dres to the rounded dx -> (dx_total, dw, dxT or empty)",
+        py::arg("dys"), py::arg("x"), py::arg("weight"), py::arg("invrms"),
+        py::arg("dres") = py::none(), py::arg("want_t") = false);
   m.def("rope_fwd", &rope_fwd, "RoPE forward");
   m.def("rope_bwd", &rope_bwd, "RoPE backward");
+  m.def("rope_bwd_t", &rope_bwd_t,
+        "RoPE backward that also writes dx^T [H*D, B*S] when aligned (D = 128, B*S % 64 == "
+        "0, bf16): (dx, dxT), else (dx,)");
   m.def("swiglu_fwd", &swiglu_fwd, "SwiGLU forward");
   m.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward (dgate, dup)");
+  m.def("swiglu_bwd_t", &swiglu_bwd_t,
+        "SwiGLU backward that also writes dgate^T, dup^T [I, T] when aligned (T % 64 == 0, "
+        "I % 128 == 0, bf16): (dgate, dup, dgateT, dupT), else (dgate, dup)");
   m.def("cross_entropy_fwd", &cross_entropy_fwd, "fused CE forward (loss_sum, lse, count)");
   m.def("cross_entropy_bwd", &cross_entropy_bwd, "fused CE backward (dlogits)");
   m.def("fused_adamw", &fused_adamw, "fused mixed-precision AdamW");

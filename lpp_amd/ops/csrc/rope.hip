@@ -12,6 +12,7 @@
 // Reference op: SURVEY.md §2.7 "RoPE apply"; position_ids threading at
 // models/llama_ds_mp_wrap.py:25,37,148. Oracle: lpp_amd.ops.apply_rope_ref.
 #include "common.h"
+#include "transpose_tile.h"
 
 namespace lpp {
 
@@ -50,6 +51,58 @@ __global__ void rope_kernel(const T* __restrict__ x, const float* __restrict__ c
   }
 }
 
+// Backward rotation that also writes dx^T for the wgrad GEMM of q_proj /
+// k_proj: x viewed as [T = B*S, H*D] with D = 128, one workgroup per 64-token
+// x one-head tile (the pair (d, d + 64) of a head sits inside the tile).  A
+// thread holds eight bf16 of one half; the partner half lives in lane ^ 8 of
+// the same row.  The rotation is rope_kernel<T, true>'s expressions; the
+// natural store is unchanged and the tile also goes out transposed
+// (transpose_tile.h).  Requires T % 64 == 0.
+__global__ __launch_bounds__(256) void rope_bwd_t_kernel(
+    const __hip_bfloat16* __restrict__ x, const float* __restrict__ cos_t,
+    const float* __restrict__ sin_t, __hip_bfloat16* __restrict__ y,
+    short* __restrict__ yT, int T, int S, int C /* H*128 */, int pos_offset) {
+  __shared__ __attribute__((aligned(16))) char img[kTTImgBytes];
+  using T_ = __hip_bfloat16;
+  using PV = Pack<T_, 8>;
+  constexpr int half = 64;
+
+  const int r0 = blockIdx.y * 64;
+  const int c0 = blockIdx.x * 128;
+  const int col = tt_col();
+  const bool first = col < half;
+  const int d0 = col & (half - 1);
+
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const int row = r0 + tt_row(pass);
+    const int s = row % S;
+    const int64_t off = (int64_t)row * C + c0 + col;
+    PV own = *reinterpret_cast<const PV*>(x + off);
+    PV oth;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      reinterpret_cast<int*>(&oth)[k] = __shfl_xor(reinterpret_cast<const int*>(&own)[k], 8);
+    const float* cr = cos_t + (int64_t)(pos_offset + s) * half + d0;
+    const float* sr = sin_t + (int64_t)(pos_offset + s) * half + d0;
+    PV out;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      float c = cr[k];
+      float sn = -sr[k];
+      float a = to_f32(first ? own.v[k] : oth.v[k]);
+      float b = to_f32(first ? oth.v[k] : own.v[k]);
+      T_ y1 = from_f32<T_>(a * c - b * sn);
+      T_ y2 = from_f32<T_>(b * c + a * sn);
+      out.v[k] = first ? y1 : y2;
+    }
+    *reinterpret_cast<PV*>(y + off) = out;
+    tt_stage(img, *reinterpret_cast<const bf16x8_t*>(&out), pass);
+  }
+  __syncthreads();
+  tt_store(img, yT, T, r0, c0);
+}
+
 template <bool BWD>
 at::Tensor rope_launch(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, int64_t pos_offset) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4, "rope: x must be [B,S,H,D]");
@@ -79,4 +132,32 @@ at::Tensor rope_fwd(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, int64_t po
 
 at::Tensor rope_bwd(at::Tensor dy, at::Tensor cos_t, at::Tensor sin_t, int64_t pos_offset) {
   return lpp::rope_launch<true>(dy, cos_t, sin_t, pos_offset);
+}
+
+// rope_bwd that also returns dx^T ([H*D, B*S]) when x is bf16 with D == 128
+// and B*S % 64 == 0: {dx, dxT}.  Any other shape runs rope_kernel and
+// returns {dx}.
+std::vector<at::Tensor> rope_bwd_t(at::Tensor dy, at::Tensor cos_t, at::Tensor sin_t,
+                                   int64_t pos_offset) {
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 4,
+              "rope: x must be [B,S,H,D]");
+  const int64_t B = dy.size(0), S = dy.size(1), H = dy.size(2), D = dy.size(3);
+  const int64_t T = B * S, C = H * D;
+  if (dy.scalar_type() != at::kBFloat16 || D != 128 || T == 0 || T % 64 != 0 ||
+      T / 64 > 65535 || T > INT32_MAX || C > INT32_MAX)
+    return {lpp::rope_launch<true>(dy, cos_t, sin_t, pos_offset)};
+  TORCH_CHECK(cos_t.is_contiguous() && sin_t.is_contiguous());
+  TORCH_CHECK(cos_t.scalar_type() == at::kFloat && sin_t.scalar_type() == at::kFloat);
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == D / 2 && sin_t.sizes() == cos_t.sizes(),
+              "rope: cos/sin must be [Smax, D/2]");
+  TORCH_CHECK(pos_offset >= 0 && cos_t.size(0) >= pos_offset + S, "rope cache too short");
+  auto dx = at::empty_like(dy);
+  auto dxT = at::empty({C, T}, dy.options());
+  dim3 grid((unsigned)H, (unsigned)(T / 64));
+  hipLaunchKernelGGL(lpp::rope_bwd_t_kernel, grid, dim3(256), 0, lpp::current_stream(),
+                     (const __hip_bfloat16*)dy.data_ptr(), cos_t.data_ptr<float>(),
+                     sin_t.data_ptr<float>(), (__hip_bfloat16*)dx.data_ptr(),
+                     (short*)dxT.data_ptr(), (int)T, (int)S, (int)C, (int)pos_offset);
+  LPP_CHECK_HIP(hipGetLastError());
+  return {dx, dxT};
 }

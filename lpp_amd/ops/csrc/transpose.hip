@@ -13,6 +13,7 @@
 // both the row-wise writes and column-wise reads are bank-conflict-free
 // (32 banks x 4B on CDNA4).
 #include "common.h"
+#include "transpose_tile.h"
 
 namespace lpp {
 
@@ -86,73 +87,24 @@ __global__ __launch_bounds__(256) void transpose2d_kernel(
 // ((d>>3)^d)&7 block swizzle, the scheme the attention kernels used before
 // their transposing LDS reads) — every LDS access is b64/b128 vectorised:
 // load b128 -> in-register quad transpose -> 2x ds_write_b64 -> ds_read_b128
-// -> global b128 store.  v1 above stays for ragged shapes and fp16.
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(2))) int int2v_t;
-
-__device__ __forceinline__ int t2swz(int d, int r) {
-  return (d * 64 + (r ^ ((((d >> 3) ^ d) & 7) << 3))) * 2;
-}
+// -> global b128 store (transpose_tile.h, shared with the backward
+// producers).  v1 above stays for ragged shapes and fp16.
 
 __global__ __launch_bounds__(256) void transpose2d_v2_kernel(
     const short* __restrict__ in, short* __restrict__ out, int R, int C) {
-  __shared__ __attribute__((aligned(16))) char img[128 * 64 * 2];  // 16 KB
-
-  const int tid = threadIdx.x;
-  const int wid = tid >> 6;
-  const int lane = tid & 63;
-  const int st_r = (lane >> 4) & 3;    // quad row 0..3
-  const int st_c = 8 * (lane & 15);    // col pack 0..120
+  __shared__ __attribute__((aligned(16))) char img[kTTImgBytes];  // 16 KB
 
   const int r0 = blockIdx.y * 64;
   const int c0 = blockIdx.x * 128;
 
 #pragma unroll
   for (int pass = 0; pass < 4; ++pass) {
-    const int r = 4 * wid + 16 * pass + st_r;
     const bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(
-        in + (int64_t)(r0 + r) * C + c0 + st_c);
-    // 4x4 dword butterfly across the lane quad {l, l^16, l^32, l^48}
-    int dw[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dw[k] = reinterpret_cast<const int*>(&v)[k];
-    {
-      int t0 = __shfl_xor(dw[(st_r & 1) ^ 1], 16);
-      int t1 = __shfl_xor(dw[((st_r & 1) ^ 1) | 2], 16);
-      if (st_r & 1) { dw[0] = t0; dw[2] = t1; } else { dw[1] = t0; dw[3] = t1; }
-    }
-    {
-      int lo = (st_r & 2) ? 0 : 2;
-      int t0 = __shfl_xor(dw[lo], 32);
-      int t1 = __shfl_xor(dw[lo + 1], 32);
-      dw[lo] = t0; dw[lo + 1] = t1;
-    }
-    const int rq = 4 * wid + 16 * pass;  // quad's first row
-    const int d0 = st_c + 2 * st_r;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int d = d0 + e;
-      unsigned w01 = e ? (((unsigned)dw[0] >> 16) | ((unsigned)dw[1] & 0xffff0000u))
-                       : (((unsigned)dw[0] & 0xffffu) | ((unsigned)dw[1] << 16));
-      unsigned w23 = e ? (((unsigned)dw[2] >> 16) | ((unsigned)dw[3] & 0xffff0000u))
-                       : (((unsigned)dw[2] & 0xffffu) | ((unsigned)dw[3] << 16));
-      int2v_t pair = {(int)w01, (int)w23};
-      *reinterpret_cast<int2v_t*>(img + t2swz(d, rq)) = pair;
-    }
+        in + (int64_t)(r0 + tt_row(pass)) * C + c0 + tt_col());
+    tt_stage(img, v, pass);
   }
   __syncthreads();
-
-  // store: out[c0+d][r0 + 8p ..] — 8 consecutive lanes cover packs 0..7 of
-  // one out row (a full 128-B line per 8-lane group); b128 LDS reads are
-  // one swizzled 8-block each, banks spread by p^e within the group.
-#pragma unroll
-  for (int pass = 0; pass < 4; ++pass) {
-    const int d = 32 * pass + (tid >> 3);
-    const int p = tid & 7;
-    const bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(img + t2swz(d, 8 * p));
-    *reinterpret_cast<bf16x8_t*>(out + (int64_t)(c0 + d) * R + r0 + 8 * p) = v;
-  }
+  tt_store(img, out, R, r0, c0);
 }
 
 at::Tensor transpose2d(at::Tensor in) {

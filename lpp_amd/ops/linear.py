@@ -51,6 +51,70 @@ class _XTCache:
 _xt_cache = _XTCache()
 
 
+class _HandoffCache:
+    """Transposed wgrad operands handed over by the kernel that produced dy.
+
+    The memory-bound backward kernels (swiglu, rope, the fused norm backward)
+    write their gradient and its transposed image together; the producer
+    registers ``(natural, image)`` here and the wgrad that consumes that very
+    gradient takes the image instead of running ``transpose2d``.  Looked up
+    by (data_ptr, shape, dtype) with a STRONG reference held, the same rule
+    as ``_XTCache`` and for the same reason.  A hit removes the entry (one
+    consumer per gradient); at most ``CAPACITY`` entries, oldest dropped
+    first, so an image nobody takes does not outlive the next few
+    producers."""
+
+    CAPACITY = 4
+    __slots__ = ("entries", "hits", "misses")
+
+    def __init__(self):
+        self.entries = []  # [(natural, image)], oldest first
+        self.hits = 0
+        self.misses = 0
+
+    def put(self, natural: torch.Tensor, image: torch.Tensor) -> None:
+        self.entries.append((natural, image))
+        if len(self.entries) > self.CAPACITY:
+            del self.entries[0]
+
+    def take(self, dy2: torch.Tensor):
+        """The image registered for ``dy2`` (removed), or None."""
+        for i, (nat, img) in enumerate(self.entries):
+            if (nat.data_ptr() == dy2.data_ptr() and nat.shape == dy2.shape
+                    and nat.dtype == dy2.dtype):
+                del self.entries[i]
+                self.hits += 1
+                return img
+        self.misses += 1
+        return None
+
+    def clear(self):
+        self.entries.clear()
+
+    def __len__(self):
+        return len(self.entries)
+
+
+_handoff = _HandoffCache()
+
+
+def bwd_handoff_enabled() -> bool:
+    """Producers write the transposed wgrad operand and the norm backward
+    fuses the gradient adds (default).  LPP_BWD_HANDOFF=0 restores separate
+    transposes, the plain rmsnorm_bwd and autograd's elementwise adds."""
+    return os.environ.get("LPP_BWD_HANDOFF", "1") == "1"
+
+
+def register_handoff(natural: torch.Tensor, image: torch.Tensor) -> None:
+    """Called by a producer: ``image`` is ``natural`` viewed [T, C], transposed."""
+    _handoff.put(natural.view(image.shape[1], image.shape[0]), image)
+
+
+def clear_backward_caches() -> None:
+    _xt_cache.clear()
+    _handoff.clear()
+
+
 def _wgrad_pre_enabled() -> bool:
     return os.environ.get("LPP_WGRAD_PRE", "1") == "1"
 
@@ -119,7 +183,9 @@ class _LinearWgradF32(torch.autograd.Function):
             # layout) at the cost of two HBM-speed LDS-tiled transposes;
             # the x transpose is shared across sibling projections.
             xT = _xt_cache.get(ext, x2)
-            dyT = ext.transpose2d(dy2)
+            dyT = _handoff.take(dy2) if bwd_handoff_enabled() else None
+            if dyT is None:
+                dyT = ext.transpose2d(dy2)
             if _wgrad_bf16d_enabled():
                 ext.accum_bf16_f32(ctx.main_grad.view(-1),
                                    torch.matmul(dyT, xT.t()).view(-1))

@@ -19,6 +19,7 @@ from typing import Tuple
 import torch
 
 from . import use_hip, extension
+from .linear import bwd_handoff_enabled, register_handoff
 
 _CACHE: dict = {}
 
@@ -68,8 +69,14 @@ class _RopeHIP(torch.autograd.Function):
         cos, sin = ctx.saved_tensors
         ext = extension()
         # RoPE is a rotation; backward rotates by -theta == sin sign flip.
-        dx = ext.rope_bwd(dy.contiguous(), cos, sin, ctx.pos_offset)
-        return dx, None, None, None
+        if not bwd_handoff_enabled():
+            dx = ext.rope_bwd(dy.contiguous(), cos, sin, ctx.pos_offset)
+            return dx, None, None, None
+        # aligned shapes also get dx^T for the q_proj / k_proj wgrad
+        out = ext.rope_bwd_t(dy.contiguous(), cos, sin, ctx.pos_offset)
+        if len(out) == 2:
+            register_handoff(out[0], out[1])
+        return out[0], None, None, None
 
 
 def apply_rope(

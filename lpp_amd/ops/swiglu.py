@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import use_hip, extension
+from .linear import bwd_handoff_enabled, register_handoff
 
 
 def swiglu_ref(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
@@ -30,8 +31,16 @@ class _SwiGLUHIP(torch.autograd.Function):
     def backward(ctx, dy):
         gate, up = ctx.saved_tensors
         ext = extension()
-        dgate, dup = ext.swiglu_bwd(dy.contiguous(), gate, up)
-        return dgate, dup
+        if not bwd_handoff_enabled():
+            dgate, dup = ext.swiglu_bwd(dy.contiguous(), gate, up)
+            return dgate, dup
+        # aligned shapes also get dgate^T / dup^T, which the gate_proj /
+        # up_proj wgrads take instead of transposing
+        out = ext.swiglu_bwd_t(dy.contiguous(), gate, up)
+        if len(out) == 4:
+            register_handoff(out[0], out[2])
+            register_handoff(out[1], out[3])
+        return out[0], out[1]
 
 
 def swiglu(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
