@@ -194,13 +194,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
           for (int r = 0; r < 16; ++r) {
             const int kv = kv0 + t2 * 32 + crow32(r, hi2);
             const bool ok = (kv <= qrow) && (kv < S);
-            const float e = exp2f(fmaf(st[r], c, -Lq));
+            const float e = attn_exp2(fmaf(st[r], c, -Lq));
             ds[r] = (ok ? e : 0.f) * (dpt[r] - Dq);
           }
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            ds[r] = exp2f(fmaf(st[r], c, -Lq)) * (dpt[r] - Dq);
+            ds[r] = attn_exp2(fmaf(st[r], c, -Lq)) * (dpt[r] - Dq);
         }
 
         bf16x8 dsa[2];
@@ -244,7 +244,7 @@ constexpr int KV_LD_OFF = attn_lds_bytes(KV_IMAGES);                   // float 
 constexpr int KV_D_OFF = KV_LD_OFF + 2 * KV_QT * (int)sizeof(float);   // float D[2][64]
 constexpr int KV_LDS_BYTES = KV_D_OFF + 2 * KV_QT * (int)sizeof(float);
 
-// gfx950 (hipcc -O3): NumVgprs 210, ScratchSize 0, Occupancy 2 waves/SIMD.
+// gfx950 (hipcc -O3): NumVgprs 204, ScratchSize 0, Occupancy 2 waves/SIMD.
 // 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
 __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
@@ -363,14 +363,14 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
             for (int r = 0; r < 4; ++r) {
               const int q = qt0 + q0 + r;
               const bool ok = (kvrow < S) && (q >= kvrow) && (q < S);
-              const float e = exp2f(fmaf(st[qs][r], c, -Lr[r]));
+              const float e = attn_exp2(fmaf(st[qs][r], c, -Lr[r]));
               p[qs][r] = ok ? e : 0.f;
               ds[qs][r] = p[qs][r] * (dpt[qs][r] - Dr[r]);
             }
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              p[qs][r] = exp2f(fmaf(st[qs][r], c, -Lr[r]));
+              p[qs][r] = attn_exp2(fmaf(st[qs][r], c, -Lr[r]));
               ds[qs][r] = p[qs][r] * (dpt[qs][r] - Dr[r]);
             }
           }

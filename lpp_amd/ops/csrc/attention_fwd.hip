@@ -175,7 +175,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     float ps = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
-      p[i] = exp2f(fmaf(ms[i], c, -m_new));
+      p[i] = attn_exp2(fmaf(ms[i], c, -m_new));
       ps += p[i];
     }
     {

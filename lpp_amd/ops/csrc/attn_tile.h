@@ -43,6 +43,15 @@ __device__ __forceinline__ short f32_to_bf16(float f) {
   __hip_bfloat16 h = __float2bfloat16(f);
   return *reinterpret_cast<short*>(&h);
 }
+// 2^x for the P of the tile loops: one v_exp_f32.  exp2f() under plain -O3
+// wraps that instruction in five more (compare, select, add, select, ldexp)
+// that rescale arguments below -126 so the result comes out as a subnormal.
+// Contract: x = -inf (a masked score) gives exactly 0, as exp2f does; a result
+// below 2^-126 is flushed to 0 where exp2f returned a subnormal; every other
+// result has the same bits.  Such a P is below 1.2e-38 beside a row sum of at
+// least 2^-8 (defer-max threshold) and accumulators many orders larger, so no
+// output bit moves unless an accumulator is itself subnormal-sized.
+__device__ __forceinline__ float attn_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float as_f(int v) { return __int_as_float(v); }
 __device__ __forceinline__ int as_i(float v) { return __float_as_int(v); }
 
