@@ -181,6 +181,11 @@ class TrainConfig:
     # converted checkpoint dir carrying tokenizer files)
     tokenizer_path: str = ""
     data_field: Optional[str] = None  # unwrap nested mixing-dataset items
+    # Sequence packing (data_kind jsonl only): several examples share one
+    # seq_len row (data.PackedRowsDataset), attention is confined to each by
+    # the document-masked kernels, and doc_start [mbs, S] int32 follows the
+    # hidden state between stages.  A step then counts rows, not examples.
+    pack_sequences: bool = False
     # shell command run by rank 0 after each checkpoint save, with {dir}
     # substituted (reference: ./s5cmd sync to S3, trainer_base_ds_mp.py:220)
     save_hook_cmd: str = ""

@@ -388,3 +388,81 @@ class SimpleTokenizer:
             out[i, : len(r)] = torch.tensor(r, dtype=torch.long)
             mask[i, : len(r)] = 1
         return {"input_ids": out, "attention_mask": mask}
+
+
+class PackedRowsDataset(Dataset):
+    """Sequence packing: several prompt/completion examples share one row of
+    ``seq_len`` tokens instead of each being padded to it.
+
+    Every example is tokenised once with ``Seq2SeqToCausalLM`` (true lengths,
+    truncated at ``seq_len`` like ``TextCollator`` does) and placed at
+    construction by first-fit-decreasing: examples by decreasing length (ties
+    by index), each into the first row with room.  The placement depends only
+    on the lengths, so every rank that builds the dataset gets the same rows.
+
+    Item: ``{"input_ids": [S], "labels": [S], "doc_start": [S] int32}``.
+    ``doc_start[i]`` is the row index of the first token of the document that
+    holds token ``i`` (``ops.DocLayout``); attention is confined to each
+    document by the kernels.  Labels are ``completion_labels`` per example,
+    and the first token of every document is -100 as well, so the shifted
+    cross-entropy never asks the last token of one document to predict the
+    first token of the next.  What is left of a row is padding: pad ids,
+    -100 labels and one-token documents.
+
+    Items have a fixed shape, so the default collate stacks them and the batch
+    dimension stays static; that is why packing is a dataset and not a
+    collator (the pipeline's p2p shapes are fixed)."""
+
+    _CHUNK = 256  # examples per tokeniser call (bounds the padded scratch batch)
+
+    def __init__(self, dataset, tokenizer, seq_len: int, field: Optional[str] = None):
+        convert = Seq2SeqToCausalLM(tokenizer, seq_len)
+        pad_id = tokenizer.pad_token_id
+        docs = []  # (ids [n], labels [n]) per example, in dataset order
+        for lo in range(0, len(dataset), self._CHUNK):
+            items = [dataset[i] for i in range(lo, min(lo + self._CHUNK, len(dataset)))]
+            enc = convert([it[field] if field else it for it in items])
+            labels = completion_labels(enc["input_ids"], enc["prompt_lens"], pad_id,
+                                       lengths=enc["lengths"])
+            for r, n in enumerate(enc["lengths"].tolist()):
+                n = min(int(n), seq_len)
+                lab = labels[r, :n].clone()
+                lab[0] = IGNORE_INDEX
+                docs.append((enc["input_ids"][r, :n].clone(), lab))
+        self.seq_len = seq_len
+        self.num_examples = len(docs)
+        # first-fit-decreasing; placement[row] = example indices in row order
+        order = sorted(range(len(docs)), key=lambda i: (-docs[i][0].numel(), i))
+        self.placement: List[List[int]] = []
+        room: List[int] = []
+        for i in order:
+            n = docs[i][0].numel()
+            for row, free in enumerate(room):
+                if n <= free:
+                    break
+            else:
+                row = len(room)
+                room.append(seq_len)
+                self.placement.append([])
+            self.placement[row].append(i)
+            room[row] -= n
+        self.rows = []
+        for members in self.placement:
+            ids = torch.full((seq_len,), pad_id, dtype=torch.long)
+            labels = torch.full((seq_len,), IGNORE_INDEX, dtype=torch.long)
+            doc_start = torch.arange(seq_len, dtype=torch.int32)
+            at = 0
+            for i in members:
+                n = docs[i][0].numel()
+                ids[at : at + n] = docs[i][0]
+                labels[at : at + n] = docs[i][1]
+                doc_start[at : at + n] = at
+                at += n
+            self.rows.append({"input_ids": ids, "labels": labels, "doc_start": doc_start})
+        self.real_tokens = sum(seq_len - free for free in room)
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, idx) -> Dict[str, torch.Tensor]:
+        return self.rows[idx]

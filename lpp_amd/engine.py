@@ -148,7 +148,14 @@ class PipelineEngine:
         hidden = config.model.hidden_size
         act_shape = (self.micro_batch_size, self.seq_len, hidden)
         comm_dtype = self.dtype if self.dtype != torch.float32 else torch.float32
-        self.p2p = PipeP2P(grid, act_shape, comm_dtype, device)
+        # Sequence packing (data.PackedRowsDataset): the first stage takes
+        # doc_start [mbs, S] from its batch, every later stage receives it
+        # behind the hidden state; each stage builds ONE ops.DocLayout per
+        # microbatch, shared by all its layers.
+        self.pack_sequences = bool(getattr(config, "pack_sequences", False))
+        doc_shape = (self.micro_batch_size, self.seq_len) if self.pack_sequences else None
+        self.p2p = PipeP2P(grid, act_shape, comm_dtype, device, doc_shape=doc_shape)
+        self._fwd_doc_start = None  # doc_start of the latest forward, for the send
 
         opt_cfg = config.optimizer
         self.zero1 = bool(getattr(config, "zero_stage", 0) == 1 and grid.dp_degree > 1)
@@ -288,21 +295,43 @@ class PipelineEngine:
                 out[k] = v
         return out
 
+    def _doc_layout(self, batch, recv):
+        """(activation, DocLayout or None) of one microbatch: doc_start comes
+        from the batch on the first stage (validated there, once per
+        microbatch) and with the activation on every later one."""
+        if not self.pack_sequences:
+            self._fwd_doc_start = None
+            return recv, None
+        from .ops import DocLayout
+
+        if batch is not None:
+            if "doc_start" not in batch:
+                raise ValueError("pack_sequences needs batches with doc_start "
+                                 "(data.PackedRowsDataset)")
+            doc_start, validate = batch["doc_start"], True
+        else:
+            recv, doc_start = recv
+            validate = False
+        docs = DocLayout(doc_start, validate=validate)
+        self._fwd_doc_start = docs.doc_start
+        return recv, docs
+
     # -- microbatch fwd/bwd ------------------------------------------------
-    def _forward_step(self, recv_act: Optional[torch.Tensor], data_iter):
+    def _forward_step(self, recv_act, data_iter):
         """Returns (input_tensor_for_grad, backward_handle, loss_detached)."""
         if self.is_first_stage:
             batch = self._next_batch(data_iter)
             x = batch["input_ids"]
             inp = None
             first_batch = batch
+            _, docs = self._doc_layout(batch, None)
         else:
-            x = recv_act
+            x, docs = self._doc_layout(None, recv_act)
             x.requires_grad_(True)
             inp = x
             first_batch = None
 
-        out = self.module(x)
+        out = self.module(x) if docs is None else self.module(x, docs=docs)
 
         if self.is_last_stage:
             if self.is_first_stage:
@@ -426,7 +455,7 @@ class PipelineEngine:
                 losses.append(loss)
             if not last:
                 with timers.section("p2p"):
-                    do_send(self.p2p.isend_forward(handle))
+                    do_send(self.p2p.isend_forward(handle, self._fwd_doc_start))
             pending.append((inp, handle))
             self._pending_dbg = tuple(range(len(pending)))
 
@@ -443,7 +472,7 @@ class PipelineEngine:
                 losses.append(loss)
             if not last:
                 with timers.section("p2p"):
-                    do_send(self.p2p.isend_forward(handle))
+                    do_send(self.p2p.isend_forward(handle, self._fwd_doc_start))
             pending.append((inp, handle))
             run_backward(take_grad())
 
@@ -482,8 +511,12 @@ class PipelineEngine:
             if self.is_first_stage:
                 batch = self._next_batch(data_iter)
                 x = batch["input_ids"]
-            out = self.module(x)
-            self.p2p.send_forward(out if not self.is_last_stage else None)
+                _, docs = self._doc_layout(batch, None)
+            else:
+                x, docs = self._doc_layout(None, x)
+            out = self.module(x) if docs is None else self.module(x, docs=docs)
+            self.p2p.send_forward(out if not self.is_last_stage else None,
+                                  self._fwd_doc_start)
             if self.is_last_stage:
                 if self.is_first_stage:
                     labels = batch["labels"]

@@ -222,9 +222,14 @@ class LlamaAttention(nn.Module):
 
     def forward(self, x: torch.Tensor, cache: Optional["KVCache"] = None,
                 x_k: Optional[torch.Tensor] = None,
-                x_v: Optional[torch.Tensor] = None) -> torch.Tensor:
+                x_v: Optional[torch.Tensor] = None,
+                docs: Optional["ops.DocLayout"] = None) -> torch.Tensor:
         # x_k / x_v: aliases of x for k_proj / v_proj (ops.rmsnorm_fork), so
         # the three input gradients reach the norm backward unsummed
+        # docs: document layout of packed rows (training only); RoPE keeps the
+        # absolute row positions (see ops.causal_attention)
+        if docs is not None and cache is not None:
+            raise ValueError("docs (packed rows) cannot be combined with a KV cache")
         B, S, _ = x.shape
         q = self.q_proj(x).view(B, S, self.num_heads, self.head_dim)
         k = self.k_proj(x if x_k is None else x_k).view(
@@ -295,7 +300,7 @@ class LlamaAttention(nn.Module):
         q = ops.apply_rope(q, cos, sin, pos_offset=pos)
         k = ops.apply_rope(k, cos, sin, pos_offset=pos)
         if cache is None:
-            o = ops.causal_attention(q, k, v)  # [B,S,H,D]
+            o = ops.causal_attention(q, k, v, docs=docs)  # [B,S,H,D]
         else:
             total = cache.append(k, v)
             if S == total:
@@ -347,6 +352,8 @@ class DecoderLayerPipe(nn.Module):
     whole layer (interval semantics handled by the engine).
     """
 
+    takes_docs = True  # PipelineModule passes the packed-row layout to such layers
+
     def __init__(self, cfg: ModelConfig, activation_checkpointing: bool = False):
         super().__init__()
         self.self_attn = LlamaAttention(cfg)
@@ -356,15 +363,18 @@ class DecoderLayerPipe(nn.Module):
         self.activation_checkpointing = activation_checkpointing
 
     def _forward_impl(self, hidden: torch.Tensor,
-                      cache: Optional[KVCache] = None) -> torch.Tensor:
+                      cache: Optional[KVCache] = None,
+                      docs: Optional["ops.DocLayout"] = None) -> torch.Tensor:
         if cache is None and ops.rmsnorm_fork_applies(hidden) and (
                 hidden.requires_grad or self.input_layernorm.weight.requires_grad):
-            return self._forward_fork(hidden)
-        hidden = hidden + self.self_attn(self.input_layernorm(hidden), cache=cache)
+            return self._forward_fork(hidden, docs=docs)
+        hidden = hidden + self.self_attn(self.input_layernorm(hidden), cache=cache,
+                                         docs=docs)
         hidden = hidden + self.mlp(self.post_attention_layernorm(hidden))
         return hidden
 
-    def _forward_fork(self, hidden: torch.Tensor) -> torch.Tensor:
+    def _forward_fork(self, hidden: torch.Tensor,
+                      docs: Optional["ops.DocLayout"] = None) -> torch.Tensor:
         """GPU training path: same forward values, but each norm hands one
         alias of its output to every consumer, so its backward receives the
         partial gradients and the residual gradient unsummed and fuses the
@@ -376,7 +386,7 @@ class DecoderLayerPipe(nn.Module):
         want_t = getattr(hidden, "_lpp_decoder_out", False)
         hidden, xq, xk, xv = ops.rmsnorm_fork(
             hidden, ln.weight, ln.variance_epsilon, 3, want_t)
-        hidden = hidden + self.self_attn(xq, x_k=xk, x_v=xv)
+        hidden = hidden + self.self_attn(xq, x_k=xk, x_v=xv, docs=docs)
         ln = self.post_attention_layernorm
         hidden, xg, xu = ops.rmsnorm_fork(hidden, ln.weight, ln.variance_epsilon, 2, True)
         hidden = hidden + self.mlp(xg, x_up=xu)
@@ -384,12 +394,17 @@ class DecoderLayerPipe(nn.Module):
         return hidden
 
     def forward(self, hidden: torch.Tensor,
-                cache: Optional[KVCache] = None) -> torch.Tensor:
+                cache: Optional[KVCache] = None,
+                docs: Optional["ops.DocLayout"] = None) -> torch.Tensor:
+        if docs is not None and cache is not None:
+            raise ValueError("docs (packed rows) cannot be combined with a KV cache")
         if self.activation_checkpointing and self.training and hidden.requires_grad:
+            # docs rides into the recompute as an argument of the checkpoint
             return torch.utils.checkpoint.checkpoint(
-                self._forward_impl, hidden, use_reentrant=False, preserve_rng_state=False
+                self._forward_impl, hidden, None, docs,
+                use_reentrant=False, preserve_rng_state=False
             )
-        return self._forward_impl(hidden, cache=cache)
+        return self._forward_impl(hidden, cache=cache, docs=docs)
 
     @staticmethod
     def spec_param_count(cfg: ModelConfig, activation_checkpointing: bool = False) -> int:
@@ -541,14 +556,19 @@ class LlamaForCausalLM(nn.Module):
             [s.build() for s in get_layers_from_config(cfg, activation_checkpointing)]
         )
 
-    def forward(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, input_ids: torch.Tensor,
+                docs: Optional["ops.DocLayout"] = None) -> torch.Tensor:
         x = input_ids
         for layer in self.layers:
-            x = layer(x)
+            if docs is not None and getattr(layer, "takes_docs", False):
+                x = layer(x, docs=docs)
+            else:
+                x = layer(x)
         return x
 
-    def compute_loss(self, input_ids: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        return loss_fn(self.forward(input_ids), labels)
+    def compute_loss(self, input_ids: torch.Tensor, labels: torch.Tensor,
+                     docs: Optional["ops.DocLayout"] = None) -> torch.Tensor:
+        return loss_fn(self.forward(input_ids, docs=docs), labels)
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int,

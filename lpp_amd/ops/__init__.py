@@ -98,7 +98,7 @@ from .rope import (build_rope_cache, apply_rope, apply_rope_positions,  # noqa: 
                    apply_rope_cs)
 from .swiglu import swiglu  # noqa: E402
 from .cross_entropy import shifted_cross_entropy  # noqa: E402
-from .attention import (causal_attention, decode_attention,  # noqa: E402
+from .attention import (DocLayout, causal_attention, decode_attention,  # noqa: E402
                         decode_attention_ref, decode_attention_hip_supported)
 
 __all__ = [
@@ -112,6 +112,7 @@ __all__ = [
     "swiglu",
     "shifted_cross_entropy",
     "causal_attention",
+    "DocLayout",
     "decode_attention",
     "decode_attention_ref",
     "decode_attention_hip_supported",

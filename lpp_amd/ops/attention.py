@@ -11,17 +11,102 @@ Dispatch:
 - HIP flash-style kernel (gfx950 MFMA, online softmax) when available.
 - Otherwise torch SDPA with ``is_causal=True`` (CPU tests / A-B baseline).
 
+Packed rows (several documents in one [S] row) are described by a
+``DocLayout``: attention stays causal and is confined to each document.  The
+kernels take two int32 [B,S] tensors instead of a mask and skip the key tiles
+no query of a wave can see.
+
 Layout contract: q [B, S, H, D], k/v [B, S, Hkv, D]; returns [B, S, H, D].
 """
 
 from __future__ import annotations
+
+from typing import Optional, Sequence
 
 import torch
 
 from . import use_hip, extension, force_eager
 
 
-def causal_attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+class DocLayout:
+    """Document layout of one packed microbatch, shared by every layer of a
+    stage (build it once per microbatch, not per layer).
+
+    ``doc_start`` int32 [B,S]: ``doc_start[b,i]`` is the index in row ``b`` of
+    the first token of the document that holds token ``i``; non-decreasing
+    along ``i``, ``doc_start[b,i] <= i``, ``doc_start[b,0] == 0``, and constant
+    over each document (``doc_start[b, doc_start[b,i]] == doc_start[b,i]``).
+    Query ``i`` sees key ``j`` iff ``doc_start[b,i] <= j <= i``.  A padding
+    token is its own one-token document.
+
+    ``doc_end`` int32 [B,S], derived here on ``doc_start``'s device:
+    one past the last token of token ``j``'s document.
+    """
+
+    def __init__(self, doc_start: torch.Tensor, validate: bool = True):
+        if doc_start.dim() != 2:
+            raise ValueError(f"doc_start must be [B,S], got {tuple(doc_start.shape)}")
+        if doc_start.dtype is not torch.int32:
+            raise ValueError(f"doc_start must be int32, got {doc_start.dtype}")
+        if doc_start.shape[1] < 1:
+            raise ValueError("doc_start needs at least one token per row")
+        doc_start = doc_start.contiguous()
+        B, S = doc_start.shape
+        idx = torch.arange(S, dtype=torch.int32, device=doc_start.device)
+        if validate:
+            if bool((doc_start[:, 0] != 0).any()):
+                raise ValueError("doc_start[b, 0] must be 0")
+            if bool((doc_start < 0).any()) or bool((doc_start > idx).any()):
+                raise ValueError("doc_start[b, i] must lie in 0..i")
+            if bool((doc_start[:, 1:] < doc_start[:, :-1]).any()):
+                raise ValueError("doc_start must be non-decreasing along the row")
+            if bool((torch.gather(doc_start, 1, doc_start.long()) != doc_start).any()):
+                raise ValueError("doc_start must be constant over each document")
+        # doc_end[j] = the next document's start after j, or S: a reversed
+        # running minimum over the starts of the boundaries to the right.
+        is_first = doc_start == idx
+        nxt = torch.where(is_first, idx.expand(B, S), torch.full_like(doc_start, S))
+        nxt = torch.cat([nxt[:, 1:], torch.full_like(nxt[:, :1], S)], dim=1)
+        self.doc_start = doc_start
+        self.doc_end = torch.flip(torch.cummin(torch.flip(nxt, [1]), dim=1).values,
+                                  [1]).contiguous()
+
+    @classmethod
+    def from_lengths(cls, lengths_per_row: Sequence[Sequence[int]], S: int,
+                     device=None) -> "DocLayout":
+        """Rows given as document lengths, in order; what is left of a row
+        after its documents is padding (one-token documents)."""
+        rows = []
+        for lengths in lengths_per_row:
+            if any(int(n) < 1 for n in lengths) or sum(int(n) for n in lengths) > S:
+                raise ValueError(f"document lengths {list(lengths)} do not fit a row of {S}")
+            row, at = [], 0
+            for n in lengths:
+                row += [at] * int(n)
+                at += int(n)
+            row += list(range(at, S))
+            rows.append(row)
+        return cls(torch.tensor(rows, dtype=torch.int32, device=device))
+
+    def lengths(self):
+        """Document lengths per row, padding tokens as documents of one."""
+        out = []
+        for ds in self.doc_start.cpu().tolist():
+            firsts = [i for i, s in enumerate(ds) if s == i] + [len(ds)]
+            out.append([b - a for a, b in zip(firsts[:-1], firsts[1:])])
+        return out
+
+    def mask(self) -> torch.Tensor:
+        """The block-diagonal causal boolean mask [B,1,S,S] (True = attend):
+        the oracle's form, never built on the kernel path."""
+        S = self.doc_start.shape[1]
+        j = torch.arange(S, device=self.doc_start.device)
+        return ((j[None, None, :] >= self.doc_start[:, :, None])
+                & (j[None, None, :] <= j[None, :, None]))[:, None]
+
+
+def causal_attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                         docs: Optional[DocLayout] = None) -> torch.Tensor:
     B, S, H, D = q.shape
     Hkv = k.shape[2]
     qt = q.transpose(1, 2)  # [B,H,S,D]
@@ -31,8 +116,21 @@ def causal_attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> t
         rep = H // Hkv
         kt = kt.repeat_interleave(rep, dim=1)
         vt = vt.repeat_interleave(rep, dim=1)
-    out = torch.nn.functional.scaled_dot_product_attention(qt, kt, vt, is_causal=True)
+    if docs is None:
+        out = torch.nn.functional.scaled_dot_product_attention(qt, kt, vt, is_causal=True)
+    else:
+        _check_docs(q, docs)
+        out = torch.nn.functional.scaled_dot_product_attention(
+            qt, kt, vt, attn_mask=docs.mask())
     return out.transpose(1, 2).contiguous()
+
+
+def _check_docs(q: torch.Tensor, docs: DocLayout) -> None:
+    if tuple(docs.doc_start.shape) != (q.shape[0], q.shape[1]):
+        raise ValueError(f"DocLayout is {tuple(docs.doc_start.shape)}, "
+                         f"q has [B,S] = {tuple(q.shape[:2])}")
+    if docs.doc_start.device != q.device:
+        raise ValueError(f"DocLayout on {docs.doc_start.device}, q on {q.device}")
 
 
 def _hip_supported(q: torch.Tensor) -> bool:
@@ -61,10 +159,42 @@ class _FlashAttnHIP(torch.autograd.Function):
         return dq, dk, dv
 
 
-def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+class _FlashAttnDocsHIP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, doc_start, doc_end):
+        ext = extension()
+        o, lse = ext.attention_fwd_docs(q, k, v, doc_start)
+        ctx.save_for_backward(q, k, v, o, lse, doc_start, doc_end)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, doc_start, doc_end = ctx.saved_tensors
+        ext = extension()
+        dq, dk, dv = ext.attention_bwd_docs(do.contiguous(), q, k, v, o, lse,
+                                            doc_start, doc_end)
+        return dq, dk, dv, None, None
+
+
+def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                     docs: Optional[DocLayout] = None) -> torch.Tensor:
+    """Causal attention; with ``docs``, confined to each document of a packed
+    row (query i sees keys ``doc_start[b,i] .. i``).
+
+    q and k carry RoPE of their absolute row positions, with or without
+    ``docs``: a RoPE score depends only on ``i - j``, so under the document
+    mask absolute positions give the attention that positions reset per
+    document would, up to the rounding of the rotated q/k.  Nothing
+    position-shaped accompanies a packed row."""
+    if docs is None:
+        if use_hip(q) and _hip_supported(q):
+            return _FlashAttnHIP.apply(q.contiguous(), k.contiguous(), v.contiguous())
+        return causal_attention_ref(q, k, v)
     if use_hip(q) and _hip_supported(q):
-        return _FlashAttnHIP.apply(q.contiguous(), k.contiguous(), v.contiguous())
-    return causal_attention_ref(q, k, v)
+        _check_docs(q, docs)
+        return _FlashAttnDocsHIP.apply(q.contiguous(), k.contiguous(), v.contiguous(),
+                                       docs.doc_start, docs.doc_end)
+    return causal_attention_ref(q, k, v, docs)
 
 
 # ---------------------------------------------------------------------------

@@ -23,6 +23,15 @@ void attn_check_qkv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& 
   TORCH_CHECK(q.size(2) % k.size(2) == 0);
 }
 
+void attn_check_docs(const at::Tensor& q, const at::Tensor& d, const char* who,
+                     const char* name) {
+  TORCH_CHECK(d.scalar_type() == at::kInt, who, ": ", name, " must be int32");
+  TORCH_CHECK(d.is_contiguous(), who, ": ", name, " must be contiguous");
+  TORCH_CHECK(d.dim() == 2 && d.size(0) == q.size(0) && d.size(1) == q.size(1), who, ": ",
+              name, " must be [B,S]");
+  TORCH_CHECK(d.device() == q.device(), who, ": ", name, " must be on q's device");
+}
+
 static void attn_check_bwd(const at::Tensor& dO, const at::Tensor& q, const at::Tensor& k,
                            const at::Tensor& v, const at::Tensor& o,
                            const at::Tensor& lse2, const char* who) {
@@ -55,6 +64,42 @@ std::vector<at::Tensor> attention_bwd(at::Tensor dO, at::Tensor q, at::Tensor k,
   lpp::launch_attn_bwd_dq(dO, q, k, v, lse2, delta, dq, mode ? lpp::ATTN_MODE1_DQ : 0, 0);
   lpp::launch_attn_bwd_dkdv(dO, q, k, v, lse2, delta, dk, dv,
                             mode ? lpp::ATTN_MODE1_DKDV : 0, 0);
+  return {dq, dk, dv};
+}
+
+// Packed rows: query i of row b sees keys doc_start[b][i] .. i.  doc_start is
+// non-decreasing with doc_start[b][i] <= i, doc_end[b][j] is one past the last
+// token of key j's document (lpp_amd.ops.DocLayout validates and derives them;
+// the kernels index with them unchecked).
+std::vector<at::Tensor> attention_fwd_docs(at::Tensor q, at::Tensor k, at::Tensor v,
+                                           at::Tensor doc_start) {
+  lpp::attn_check_qkv(q, k, v, "attention_fwd_docs");
+  lpp::attn_check_docs(q, doc_start, "attention_fwd_docs", "doc_start");
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  auto o = at::empty_like(q);
+  auto lse2 = at::empty({B, H, S}, q.options().dtype(at::kFloat));
+  lpp::launch_attn_fwd(q, k, v, o, lse2,
+                       lpp::attn_order_mode() ? lpp::ATTN_MODE1_FWD : 0, 0, &doc_start);
+  return {o, lse2};
+}
+
+std::vector<at::Tensor> attention_bwd_docs(at::Tensor dO, at::Tensor q, at::Tensor k,
+                                           at::Tensor v, at::Tensor o, at::Tensor lse2,
+                                           at::Tensor doc_start, at::Tensor doc_end) {
+  lpp::attn_check_bwd(dO, q, k, v, o, lse2, "attention_bwd_docs");
+  lpp::attn_check_docs(q, doc_start, "attention_bwd_docs", "doc_start");
+  lpp::attn_check_docs(q, doc_end, "attention_bwd_docs", "doc_end");
+  const int B = q.size(0), S = q.size(1), H = q.size(2);
+  auto delta = at::empty({B, H, S}, q.options().dtype(at::kFloat));
+  lpp::launch_attn_bwd_delta(dO, o, delta);
+  auto dq = at::empty_like(q);
+  auto dk = at::empty_like(k);
+  auto dv = at::empty_like(v);
+  const int mode = lpp::attn_order_mode();
+  lpp::launch_attn_bwd_dq(dO, q, k, v, lse2, delta, dq, mode ? lpp::ATTN_MODE1_DQ : 0, 0,
+                          &doc_start);
+  lpp::launch_attn_bwd_dkdv(dO, q, k, v, lse2, delta, dk, dv,
+                            mode ? lpp::ATTN_MODE1_DKDV : 0, 0, &doc_end);
   return {dq, dk, dv};
 }
 
@@ -119,12 +164,25 @@ at::Tensor attention_lds_addresses(std::string pattern, int64_t shape, int64_t i
 // Device-timed A/B of one attention kernel under an explicit block order:
 // kernel "fwd" | "dq" | "dkdv", order (mode, G; G <= 0 = the computed group).
 // One hipEvent pair per launch; returns the ms of each of `reps` launches
-// after `warmup` untimed ones.
+// after `warmup` untimed ones.  With doc_start and doc_end (both or neither)
+// the launches are those of the packed-row (_docs) functions.
 std::vector<double> attention_time_kernel(std::string kernel, at::Tensor dO, at::Tensor q,
                                           at::Tensor k, at::Tensor v, at::Tensor o,
                                           at::Tensor lse2, int64_t mode, int64_t G,
-                                          int64_t warmup, int64_t reps) {
+                                          int64_t warmup, int64_t reps,
+                                          c10::optional<at::Tensor> doc_start,
+                                          c10::optional<at::Tensor> doc_end) {
   lpp::attn_check_bwd(dO, q, k, v, o, lse2, "attention_time_kernel");
+  TORCH_CHECK(doc_start.has_value() == doc_end.has_value(),
+              "attention_time_kernel: doc_start and doc_end come together");
+  const at::Tensor* ds = nullptr;
+  const at::Tensor* de = nullptr;
+  if (doc_start.has_value()) {
+    lpp::attn_check_docs(q, *doc_start, "attention_time_kernel", "doc_start");
+    lpp::attn_check_docs(q, *doc_end, "attention_time_kernel", "doc_end");
+    ds = &*doc_start;
+    de = &*doc_end;
+  }
   TORCH_CHECK(mode == 0 || mode == 1, "attention_time_kernel: mode 0 or 1");
   TORCH_CHECK(kernel == "fwd" || kernel == "dq" || kernel == "dkdv",
               "attention_time_kernel: kernel is fwd, dq or dkdv");
@@ -135,10 +193,10 @@ std::vector<double> attention_time_kernel(std::string kernel, at::Tensor dO, at:
   auto lse_out = at::empty_like(lse2);
   auto dk = at::empty_like(k), dv = at::empty_like(v);
   auto launch = [&] {
-    if (kernel == "fwd") lpp::launch_attn_fwd(q, k, v, o2, lse_out, (int)mode, (int)G);
+    if (kernel == "fwd") lpp::launch_attn_fwd(q, k, v, o2, lse_out, (int)mode, (int)G, ds);
     else if (kernel == "dq")
-      lpp::launch_attn_bwd_dq(dO, q, k, v, lse2, delta, dq, (int)mode, (int)G);
-    else lpp::launch_attn_bwd_dkdv(dO, q, k, v, lse2, delta, dk, dv, (int)mode, (int)G);
+      lpp::launch_attn_bwd_dq(dO, q, k, v, lse2, delta, dq, (int)mode, (int)G, ds);
+    else lpp::launch_attn_bwd_dkdv(dO, q, k, v, lse2, delta, dk, dv, (int)mode, (int)G, de);
   };
   auto stream = lpp::current_stream();
   hipEvent_t e0, e1;

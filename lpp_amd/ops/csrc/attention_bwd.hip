@@ -76,13 +76,18 @@ constexpr int DQ_QW = 32, DQ_QB = 256, DQ_KVB = ATTN_TILE_ROWS;
 enum { DQ_K, DQ_V, DQ_IMAGES };
 constexpr int DQ_LDS_BYTES = attn_lds_bytes(DQ_IMAGES);
 
-// gfx950 (hipcc -O3): NumVgprs 232, ScratchSize 0, Occupancy 2 waves/SIMD.
+// DOCS (packed rows, see attention_fwd.hip): DocStart bounds the keys of each
+// query from below; the tile loop begins at the workgroup's first start and a
+// wave skips the tiles that end before its own.  DOCS=false is the plain kernel.
+// gfx950 (hipcc -O3): DOCS=false NumVgprs 232, DOCS=true NumVgprs 232; both
+// ScratchSize 0, Occupancy 2 waves/SIMD.
 // 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
+template <bool DOCS>
 __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE2, const float* __restrict__ Delta,
-    short* __restrict__ dQ,
+    short* __restrict__ dQ, const int* __restrict__ DocStart,
     int B, int S, int H, int HKV, float c, float scale,
     int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -127,6 +132,20 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
   const int st_off[2] = {attn_stage_off<32>(wid, 0, lane), attn_stage_off<32>(wid, 1, lane)};
   const int kv_end = min(S, (qblk + 1) * DQ_QB);
 
+  // Document starts (DOCS): the lane's own and, wave-uniform, the wave's
+  // smallest (first row) and largest (last valid row) and the workgroup's
+  // smallest (first row; qblk * DQ_QB < S always), floored to a tile.
+  int qs = 0, qs_wmin = 0, qs_wmax = 0, kv_begin = 0;
+  if constexpr (DOCS) {
+    const int* ds_row = DocStart + (int64_t)b * S;
+    qs = ds_row[min(qrow, S - 1)];
+    qs_wmin = __builtin_amdgcn_readfirstlane(ds_row[min(qw0, S - 1)]);
+    qs_wmax = __builtin_amdgcn_readfirstlane(ds_row[min(qw0 + DQ_QW - 1, S - 1)]);
+    // clamped to the rows that exist, whatever the tensor holds
+    kv_begin = min(max(__builtin_amdgcn_readfirstlane(ds_row[qblk * DQ_QB]), 0),
+                   qblk * DQ_QB) & ~(DQ_KVB - 1);
+  }
+
   auto ld_tile = [&](int kv0, int pass, bf16x8& kreg, bf16x8& vreg) {
     const int row = min(kv0 + stage_row(wid, pass, st_r), S - 1);
     const int64_t rb = kv_base + (int64_t)row * sHkvD + st_c;
@@ -148,16 +167,16 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
   // template cost 57 more v_mov_b32 and measured 3-5% slower (round 5, at 254
   // VGPRs).
   bf16x8 kreg0, kreg1, vreg0, vreg1;
-  ld_tile(0, 0, kreg0, vreg0);
-  ld_tile(0, 1, kreg1, vreg1);
+  ld_tile(kv_begin, 0, kreg0, vreg0);
+  ld_tile(kv_begin, 1, kreg1, vreg1);
   write_tile(0, 0, kreg0, vreg0);
   write_tile(0, 1, kreg1, vreg1);
-  if (DQ_KVB < kv_end) {
-    ld_tile(DQ_KVB, 0, kreg0, vreg0);
-    ld_tile(DQ_KVB, 1, kreg1, vreg1);
+  if (kv_begin + DQ_KVB < kv_end) {
+    ld_tile(kv_begin + DQ_KVB, 0, kreg0, vreg0);
+    ld_tile(kv_begin + DQ_KVB, 1, kreg1, vreg1);
   }
   __syncthreads();
-  for (int kv0 = 0, cur = 0; kv0 < kv_end; kv0 += DQ_KVB, cur ^= 1) {
+  for (int kv0 = kv_begin, cur = 0; kv0 < kv_end; kv0 += DQ_KVB, cur ^= 1) {
     if (kv0 + DQ_KVB < kv_end) {
       write_tile(cur ^ 1, 0, kreg0, vreg0);
       write_tile(cur ^ 1, 1, kreg1, vreg1);
@@ -166,9 +185,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
         ld_tile(kv0 + 2 * DQ_KVB, 1, kreg1, vreg1);
       }
     }
-    if (kv0 < qw0 + DQ_QW) {  // causal: not past this wave's diagonal
+    // causal: not past this wave's diagonal; documents: not wholly before the
+    // first key any row of this wave sees (both scalar conditions)
+    if (kv0 < qw0 + DQ_QW && !(DOCS && kv0 + DQ_KVB <= qs_wmin)) {
       // wave-uniform tile class: interior tiles take the straight-line form
-      const bool need_mask = (kv0 + DQ_KVB > qw0) || (kv0 + DQ_KVB > S);
+      const bool need_mask =
+          (kv0 + DQ_KVB > qw0) || (kv0 + DQ_KVB > S) || (DOCS && kv0 < qs_wmax);
       // The tile runs as two independent 32-key halves, so only one half's
       // S^T/dP^T accumulators are live at a time and one half's softmax can
       // sit under the other half's MFMAs.  Each st/dpt element still sums
@@ -193,7 +215,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int kv = kv0 + t2 * 32 + crow32(r, hi2);
-            const bool ok = (kv <= qrow) && (kv < S);
+            const bool ok = (kv <= qrow) && (kv < S) && (!DOCS || kv >= qs);
             const float e = attn_exp2(fmaf(st[r], c, -Lq));
             ds[r] = (ok ? e : 0.f) * (dpt[r] - Dq);
           }
@@ -244,13 +266,20 @@ constexpr int KV_LD_OFF = attn_lds_bytes(KV_IMAGES);                   // float 
 constexpr int KV_D_OFF = KV_LD_OFF + 2 * KV_QT * (int)sizeof(float);   // float D[2][64]
 constexpr int KV_LDS_BYTES = KV_D_OFF + 2 * KV_QT * (int)sizeof(float);
 
-// gfx950 (hipcc -O3): NumVgprs 204, ScratchSize 0, Occupancy 2 waves/SIMD.
+// DOCS (packed rows): DocEnd[b][j] (int32 [B,S], non-decreasing, > j) is one
+// past the last token of the document that holds key j; key j is seen by
+// queries j .. DocEnd[b][j]-1.  It is monotone, so the workgroup's q loop ends
+// at the end of its last key row and a wave skips the tiles from the end of its
+// own last row on.  No per-query lookup.  DOCS=false is the plain kernel.
+// gfx950 (hipcc -O3): DOCS=false NumVgprs 204, DOCS=true NumVgprs 232; both
+// ScratchSize 0, Occupancy 2 waves/SIMD.
 // 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
+template <bool DOCS>
 __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE2, const float* __restrict__ Delta,
-    short* __restrict__ dK, short* __restrict__ dV,
+    short* __restrict__ dK, short* __restrict__ dV, const int* __restrict__ DocEnd,
     int B, int S, int H, int HKV, float c, float scale,
     int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -302,6 +331,21 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
   const int st_off[2] = {attn_stage_off<16>(wid, 0, lane), attn_stage_off<16>(wid, 1, lane)};
   const int qstart = kvblk * KV_WG;
 
+  // Document ends (DOCS): the lane's own and, wave-uniform, those of the
+  // wave's first and last key row and of the workgroup's last key row, where
+  // the q loop ends: the same value in all 512 threads (the pipeline's barrier
+  // is inside the loop) and > qstart, since DocEnd[j] > j and qstart < S.
+  int ke = S, ke_wmin = S, ke_wmax = S, q_end = S;
+  if constexpr (DOCS) {
+    const int* de_row = DocEnd + (int64_t)b * S;
+    ke = de_row[min(kvrow, S - 1)];
+    ke_wmin = __builtin_amdgcn_readfirstlane(de_row[min(kvw0, S - 1)]);
+    ke_wmax = __builtin_amdgcn_readfirstlane(de_row[min(kvw0 + KV_KW - 1, S - 1)]);
+    // clamped to (qstart, S], whatever the tensor holds
+    q_end = min(max(__builtin_amdgcn_readfirstlane(de_row[min(qstart + KV_WG - 1, S - 1)]),
+                    qstart + 1), S);
+  }
+
   for (int g = 0; g < G; ++g) {
     const int h = hkv * G + g;
     const int64_t q_base = (((int64_t)b * S) * H + h) * ATTN_D;
@@ -323,12 +367,19 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
       }
     };
 
-    attn_tile_pipeline<KV_QT>(qstart, S, ld_tile, write_tile, [&](int qt0, int cur) {
+    attn_tile_pipeline<KV_QT>(qstart, DOCS ? q_end : S, ld_tile, write_tile,
+                              [&](int qt0, int cur) {
       if (qt0 + KV_QT - 1 < kvw0) return;  // causal: tile above this wave's diagonal
+      if constexpr (DOCS) {
+        if (qt0 >= ke_wmax) return;  // documents: past the last query of this wave's keys
+      }
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         const int qh0 = qt0 + half * 32;
         if (qh0 + 31 < kvw0) continue;
+        if constexpr (DOCS) {
+          if (qh0 >= ke_wmax) continue;
+        }
         f32x4 st[2], dpt[2];
 #pragma unroll
         for (int qs = 0; qs < 2; ++qs)
@@ -351,7 +402,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
         // wave-uniform tile class.  An interior half-tile has
         // kvrow < qh0 and qh0 + 32 <= S, so every lane's kv row is inside S
         // and no element needs a mask: straight-line form.
-        const bool need_mask = (qh0 < kvw0 + KV_KW) || (qh0 + 32 > S);
+        const bool need_mask =
+            (qh0 < kvw0 + KV_KW) || (qh0 + 32 > S) || (DOCS && qh0 + 32 > ke_wmin);
         float p[2][4], ds[2][4];
 #pragma unroll
         for (int qs = 0; qs < 2; ++qs) {
@@ -362,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_kernel(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int q = qt0 + q0 + r;
-              const bool ok = (kvrow < S) && (q >= kvrow) && (q < S);
+              const bool ok = (kvrow < S) && (q >= kvrow) && (q < S) && (!DOCS || q < ke);
               const float e = attn_exp2(fmaf(st[qs][r], c, -Lr[r]));
               p[qs][r] = ok ? e : 0.f;
               ds[qs][r] = p[qs][r] * (dpt[qs][r] - Dr[r]);
@@ -422,18 +474,20 @@ void launch_attn_bwd_delta(const at::Tensor& dO, const at::Tensor& o, at::Tensor
 void launch_attn_bwd_dq(const at::Tensor& dO, const at::Tensor& q, const at::Tensor& k,
                         const at::Tensor& v, const at::Tensor& lse2,
                         const at::Tensor& delta, at::Tensor& dq, int order_mode,
-                        int order_G) {
+                        int order_G, const at::Tensor* doc_start) {
   const int B = q.size(0), S = q.size(1), H = q.size(2);
   const int HKV = k.size(2);
   const AttnScale sc = attn_scale();
   const int qblocks = (S + DQ_QB - 1) / DQ_QB;
   if (order_G <= 0)
     order_G = attn_order_group(ATTN_GROUP_WAVES * ATTN_RESIDENT_PER_XCD, qblocks);
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(qblocks * B * H), dim3(512), DQ_LDS_BYTES,
+  const int* ds = doc_start ? doc_start->data_ptr<int>() : nullptr;
+  hipLaunchKernelGGL(ds ? attn_bwd_dq_kernel<true> : attn_bwd_dq_kernel<false>,
+                     dim3(qblocks * B * H), dim3(512), DQ_LDS_BYTES,
                      current_stream(), (const short*)q.data_ptr(), (const short*)k.data_ptr(),
                      (const short*)v.data_ptr(), (const short*)dO.data_ptr(),
                      lse2.data_ptr<float>(), delta.data_ptr<float>(),
-                     (short*)dq.data_ptr(), B, S, H, HKV, sc.c, sc.scale, order_mode,
+                     (short*)dq.data_ptr(), ds, B, S, H, HKV, sc.c, sc.scale, order_mode,
                      order_G);
   LPP_CHECK_HIP(hipGetLastError());
 }
@@ -441,19 +495,21 @@ void launch_attn_bwd_dq(const at::Tensor& dO, const at::Tensor& q, const at::Ten
 void launch_attn_bwd_dkdv(const at::Tensor& dO, const at::Tensor& q, const at::Tensor& k,
                           const at::Tensor& v, const at::Tensor& lse2,
                           const at::Tensor& delta, at::Tensor& dk, at::Tensor& dv,
-                          int order_mode, int order_G) {
+                          int order_mode, int order_G, const at::Tensor* doc_end) {
   const int B = q.size(0), S = q.size(1), H = q.size(2);
   const int HKV = k.size(2);
   const AttnScale sc = attn_scale();
   const int kvblocks = (S + KV_WG - 1) / KV_WG;
   if (order_G <= 0)
     order_G = attn_order_group(ATTN_GROUP_WAVES * ATTN_RESIDENT_PER_XCD, kvblocks);
-  hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3(kvblocks * B * HKV), dim3(512),
+  const int* de = doc_end ? doc_end->data_ptr<int>() : nullptr;
+  hipLaunchKernelGGL(de ? attn_bwd_dkdv_kernel<true> : attn_bwd_dkdv_kernel<false>,
+                     dim3(kvblocks * B * HKV), dim3(512),
                      KV_LDS_BYTES, current_stream(), (const short*)q.data_ptr(),
                      (const short*)k.data_ptr(), (const short*)v.data_ptr(),
                      (const short*)dO.data_ptr(), lse2.data_ptr<float>(),
                      delta.data_ptr<float>(), (short*)dk.data_ptr(),
-                     (short*)dv.data_ptr(), B, S, H, HKV, sc.c, sc.scale, order_mode,
+                     (short*)dv.data_ptr(), de, B, S, H, HKV, sc.c, sc.scale, order_mode,
                      order_G);
   LPP_CHECK_HIP(hipGetLastError());
 }

@@ -39,10 +39,18 @@ constexpr float AF_THR = 8.0f; // defer-max threshold (exp2 domain)
 enum { AF_K, AF_V, AF_IMAGES };  // LDS images (64 KB): K, V
 constexpr int AF_LDS_BYTES = attn_lds_bytes(AF_IMAGES);
 
+// DOCS: packed rows.  DocStart[b][i] (int32 [B,S], non-decreasing in i, <= i)
+// is the first token of the document that holds token i; query i sees keys
+// DocStart[b][i] .. i.  It is monotone, so a wave's (workgroup's) smallest
+// start is the one of its first row: the pipeline begins at that tile and a
+// wave skips the tiles that end before its own first start.  DOCS=false is the
+// plain causal kernel, instruction for instruction (DocStart unused).
 // 2 waves/SIMD = one 512-thread workgroup per CU; 256 VGPRs
+template <bool DOCS>
 __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, short* __restrict__ O, float* __restrict__ LSE2,
+    const int* __restrict__ DocStart,
     int B, int S, int H, int HKV, float c /* scale*log2e */,
     int order_mode, int order_G) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -87,6 +95,20 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
 
   const int kv_end = min(S, (qblk + 1) * AF_QB);
 
+  // Document starts (DOCS): the lane's own, the wave's smallest (its first
+  // row) and largest (its last valid row), the workgroup's smallest (its first
+  // row).  The last three are wave-uniform scalars; qblk * AF_QB < S always.
+  int qs = 0, qs_wmin = 0, qs_wmax = 0, kv_begin = 0;
+  if constexpr (DOCS) {
+    const int* ds_row = DocStart + (int64_t)b * S;
+    qs = ds_row[min(qrow, S - 1)];
+    qs_wmin = __builtin_amdgcn_readfirstlane(ds_row[min(qw0, S - 1)]);
+    qs_wmax = __builtin_amdgcn_readfirstlane(ds_row[min(qw0 + AF_QW - 1, S - 1)]);
+    // clamped to the rows that exist, whatever the tensor holds
+    kv_begin = min(max(__builtin_amdgcn_readfirstlane(ds_row[qblk * AF_QB]), 0),
+                   qblk * AF_QB) & ~(AF_KVB - 1);
+  }
+
   auto ld_tile = [&](int kv0, int pass, bf16x8& kreg, bf16x8& vreg) {
     const int row = min(kv0 + stage_row(wid, pass, st_r), S - 1);
     const int64_t rb = kv_base + (int64_t)row * sHkvD + st_c;
@@ -106,10 +128,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     for (int r = 0; r < 16; ++r) o_acc[dt][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
 
-  attn_tile_pipeline<AF_KVB>(0, kv_end, ld_tile, write_tile, [&](int kv0, int cur) {
+  attn_tile_pipeline<AF_KVB>(kv_begin, kv_end, ld_tile, write_tile, [&](int kv0, int cur) {
     // causal: this wave has no work in this tile (a scalar branch: the
     // transposed reads below need every lane active)
     if (kv0 >= qw0 + AF_QW) return;
+    // documents: the tile ends before the first key any row of this wave sees
+    if constexpr (DOCS) {
+      if (kv0 + AF_KVB <= qs_wmin) return;
+    }
     // ---- S^T = K Q^T: two 32x32 tiles over kv ----
     f32x16 st[2];
 #pragma unroll
@@ -130,7 +156,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     // ---- causal / tail mask -> ms (unscaled scores, -inf where masked) ----
     // lane's q row = qrow; score reg r of tile t2 is kv0 + t2*32 + crow32(r, hi2)
     float ms[32];
-    const bool need_mask = (kv0 + AF_KVB > qw0) || (kv0 + AF_KVB > S);
+    const bool need_mask =
+        (kv0 + AF_KVB > qw0) || (kv0 + AF_KVB > S) || (DOCS && kv0 < qs_wmax);
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
@@ -139,6 +166,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
         if (need_mask) {
           const int kv = kv0 + t2 * 32 + crow32(r, hi2);
           if (kv > qrow || kv >= S) v = -INFINITY;
+          if constexpr (DOCS) {
+            if (kv < qs) v = -INFINITY;
+          }
         }
         ms[t2 * 16 + r] = v;
       }
@@ -171,11 +201,16 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     }
 
     // ---- P = exp2(ms*c - m_new); row sum; pack to PV A-fragments ----
+    // DOCS: a row whose document starts past this tile has seen no key yet
+    // (m_new = -inf, every ms = -inf); -inf - -inf would be NaN, so such a row
+    // subtracts 0 instead and gets p = exp2(-inf) = 0.  alpha above is 0 for it.
     float p[32];
     float ps = 0.f;
+    float m_sub = m_new;
+    if constexpr (DOCS) m_sub = (m_new == -INFINITY) ? 0.f : m_new;
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
-      p[i] = attn_exp2(fmaf(ms[i], c, -m_new));
+      p[i] = attn_exp2(fmaf(ms[i], c, -m_sub));
       ps += p[i];
     }
     {
@@ -219,19 +254,23 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
     LSE2[((int64_t)b * H + h) * S + qrow] = m_run + log2f(l_run);
 }
 
-// gfx950 (hipcc -O3): NumVgprs 207, ScratchSize 0, 2 waves/SIMD, 64 KB LDS.
-// order_G: see attention.h.
+// gfx950 (hipcc -O3): DOCS=false NumVgprs 207, DOCS=true NumVgprs 209; both
+// ScratchSize 0, 2 waves/SIMD, 64 KB LDS.
+// order_G: see attention.h.  doc_start: nullptr = the plain causal kernel.
 void launch_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                     at::Tensor& o, at::Tensor& lse2, int order_mode, int order_G) {
+                     at::Tensor& o, at::Tensor& lse2, int order_mode, int order_G,
+                     const at::Tensor* doc_start) {
   const int B = q.size(0), S = q.size(1), H = q.size(2);
   const int HKV = k.size(2);
   const int qblocks = (S + AF_QB - 1) / AF_QB;
   if (order_G <= 0)
     order_G = attn_order_group(ATTN_GROUP_WAVES * ATTN_RESIDENT_PER_XCD, qblocks);
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3(qblocks * B * H), dim3(512), AF_LDS_BYTES,
+  const int* ds = doc_start ? doc_start->data_ptr<int>() : nullptr;
+  hipLaunchKernelGGL(ds ? attn_fwd_kernel<true> : attn_fwd_kernel<false>,
+                     dim3(qblocks * B * H), dim3(512), AF_LDS_BYTES,
                      current_stream(), (const short*)q.data_ptr(),
                      (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                     (short*)o.data_ptr(), lse2.data_ptr<float>(), B, S, H, HKV,
+                     (short*)o.data_ptr(), lse2.data_ptr<float>(), ds, B, S, H, HKV,
                      attn_scale().c, order_mode, order_G);
   LPP_CHECK_HIP(hipGetLastError());
 }

@@ -24,6 +24,11 @@ at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor labels, at::Tensor ls
 std::vector<at::Tensor> attention_fwd(at::Tensor q, at::Tensor k, at::Tensor v);
 std::vector<at::Tensor> attention_bwd(at::Tensor dO, at::Tensor q, at::Tensor k,
                                       at::Tensor v, at::Tensor o, at::Tensor lse2);
+std::vector<at::Tensor> attention_fwd_docs(at::Tensor q, at::Tensor k, at::Tensor v,
+                                           at::Tensor doc_start);
+std::vector<at::Tensor> attention_bwd_docs(at::Tensor dO, at::Tensor q, at::Tensor k,
+                                           at::Tensor v, at::Tensor o, at::Tensor lse2,
+                                           at::Tensor doc_start, at::Tensor doc_end);
 void attention_set_block_order(int64_t mode);
 int64_t attention_get_block_order();
 at::Tensor attention_block_order(int64_t kind, int64_t nblk, int64_t nheads, int64_t G,
@@ -32,7 +37,9 @@ at::Tensor attention_lds_addresses(std::string pattern, int64_t shape, int64_t i
 std::vector<double> attention_time_kernel(std::string kernel, at::Tensor dO, at::Tensor q,
                                           at::Tensor k, at::Tensor v, at::Tensor o,
                                           at::Tensor lse2, int64_t mode, int64_t G,
-                                          int64_t warmup, int64_t reps);
+                                          int64_t warmup, int64_t reps,
+                                          c10::optional<at::Tensor> doc_start,
+                                          c10::optional<at::Tensor> doc_end);
 at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
                             at::Tensor sin_t, c10::optional<at::Tensor> positions,
@@ -89,6 +96,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adamw", &fused_adamw, "fused mixed-precision AdamW");
   m.def("attention_fwd", &attention_fwd, "flash causal attention forward (O, LSE2)");
   m.def("attention_bwd", &attention_bwd, "flash causal attention backward (dQ, dK, dV)");
+  m.def("attention_fwd_docs", &attention_fwd_docs,
+        "flash causal attention forward over packed rows (O, LSE2): query i sees keys "
+        "doc_start[b][i] .. i; doc_start int32 [B,S]",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("doc_start"));
+  m.def("attention_bwd_docs", &attention_bwd_docs,
+        "flash causal attention backward over packed rows (dQ, dK, dV); doc_end[b][j] = one "
+        "past the last token of key j's document, int32 [B,S]",
+        py::arg("dO"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+        py::arg("lse2"), py::arg("doc_start"), py::arg("doc_end"));
   m.def("attention_set_block_order", &attention_set_block_order,
         "attention block order: 0 = legacy, 1 = XCD-balanced heavy-first (default, "
         "LPP_ATTN_ORDER)", py::arg("mode"));
@@ -98,9 +114,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kind"), py::arg("nblk"), py::arg("nheads"), py::arg("G"), py::arg("mode"));
   m.def("attention_time_kernel", &attention_time_kernel,
         "hipEvent ms per launch of one attention kernel (fwd|dq|dkdv) under an explicit "
-        "block order", py::arg("kernel"), py::arg("dO"), py::arg("q"), py::arg("k"),
+        "block order; with doc_start and doc_end, of its packed-row instantiation",
+        py::arg("kernel"), py::arg("dO"), py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("o"), py::arg("lse2"), py::arg("mode"), py::arg("G") = 0,
-        py::arg("warmup") = 3, py::arg("reps") = 20);
+        py::arg("warmup") = 3, py::arg("reps") = 20, py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none());
   m.def("attention_decode", &attention_decode,
         "fused single-token decode: RoPE + KV-cache write + GQA attention over keys 0..p of "
         "each row's cache row -> o [N,1,H,128]; chunk 0 = the compiled-in chunk size",

@@ -6,6 +6,12 @@ Native replacement for the p2p DeepSpeed's PipelineEngine performs inside
 - ONE tensor per hop: the bf16 hidden state [mbs, S, H].  The reference
   ships (hidden, [B,1,S,S] fp16 mask, position_ids int64) per microbatch —
   at seq 4096 the mask alone is 32 MiB/hop of pure overhead; we ship 0.
+  With sequence packing (``doc_shape``) a second static-shape message follows
+  the hidden state on the forward channel: ``doc_start`` int32 [mbs, S], 4
+  bytes per token against 2 x hidden for the activation.  It is posted and
+  sent in the same order as the hidden state, so the pre-posted-receive
+  discipline holds unchanged; the backward channel carries gradients only.
+  Without packing no second message exists.
 - Static shapes: the engine knows (mbs, S, H) up front, so there is no
   per-tensor meta handshake on the wire; recv buffers come from the caching
   allocator.
@@ -56,13 +62,30 @@ class Pending:
         return self.buf
 
 
+class PendingGroup:
+    """Several in-flight operations posted together; ``wait()`` completes them
+    in posting order and returns their buffers as a tuple."""
+
+    __slots__ = ("parts",)
+
+    def __init__(self, *parts: Pending):
+        self.parts = parts
+
+    def wait(self):
+        return tuple(p.wait() for p in self.parts)
+
+
 class PipeP2P:
     def __init__(self, grid: ProcessGrid, act_shape: Tuple[int, ...], dtype: torch.dtype,
-                 device: torch.device):
+                 device: torch.device, doc_shape: Optional[Tuple[int, ...]] = None):
         self.grid = grid
         self.act_shape = tuple(act_shape)
         self.dtype = dtype
         self.device = device
+        # sequence packing: shape [mbs, S] of the int32 doc_start message that
+        # follows every hidden state on the forward channel (None: no such message)
+        self.doc_shape = tuple(doc_shape) if doc_shape is not None else None
+        self.fwd_messages_sent = 0  # forward-channel sends posted by this stage
         # channel groups (None outside an initialized process group, e.g.
         # single-process tests — p2p is a no-op there anyway)
         self._fwd_group = grid.pipe_fwd_group
@@ -94,20 +117,40 @@ class PipeP2P:
                 r.wait()
 
     # -- async primitives (the engine's hot path) ---------------------------
-    def isend_forward(self, tensor: torch.Tensor) -> Optional[Pending]:
-        """Post the activation send to the next stage on the fwd channel."""
+    def isend_forward(self, tensor: torch.Tensor,
+                      doc_start: Optional[torch.Tensor] = None):
+        """Post the activation send to the next stage on the fwd channel;
+        with packing, ``doc_start`` right after it."""
         if self.grid.next_rank is None:
             return None
+        if (doc_start is not None) != (self.doc_shape is not None):
+            raise ValueError("doc_start is sent exactly when the channel was built "
+                             "with doc_shape")
         t = tensor.contiguous()
         req = dist.isend(t, self.grid.next_rank, group=self._fwd_group)
-        return Pending(req, t)
+        self.fwd_messages_sent += 1
+        if doc_start is None:
+            return Pending(req, t)
+        d = doc_start.contiguous()
+        if tuple(d.shape) != self.doc_shape or d.dtype is not torch.int32:
+            raise ValueError(f"doc_start must be int32 {self.doc_shape}, got "
+                             f"{d.dtype} {tuple(d.shape)}")
+        dreq = dist.isend(d, self.grid.next_rank, group=self._fwd_group)
+        self.fwd_messages_sent += 1
+        return PendingGroup(Pending(req, t), Pending(dreq, d))
 
-    def irecv_forward(self) -> Optional[Pending]:
+    def irecv_forward(self):
+        """Post the activation receive; with packing also the ``doc_start``
+        receive, and ``wait()`` returns (hidden, doc_start)."""
         if self.grid.prev_rank is None:
             return None
         buf = self._empty()
         req = dist.irecv(buf, self.grid.prev_rank, group=self._fwd_group)
-        return Pending(req, buf)
+        if self.doc_shape is None:
+            return Pending(req, buf)
+        dbuf = torch.empty(self.doc_shape, dtype=torch.int32, device=self.device)
+        dreq = dist.irecv(dbuf, self.grid.prev_rank, group=self._fwd_group)
+        return PendingGroup(Pending(req, buf), Pending(dreq, dbuf))
 
     def isend_backward(self, grad: torch.Tensor) -> Optional[Pending]:
         """Post the gradient send to the previous stage on the bwd channel."""
@@ -125,14 +168,17 @@ class PipeP2P:
         return Pending(req, buf)
 
     # -- blocking convenience (eval/generation; not the training hot path) --
-    def send_forward(self, tensor: Optional[torch.Tensor]) -> None:
+    def send_forward(self, tensor: Optional[torch.Tensor],
+                     doc_start: Optional[torch.Tensor] = None) -> None:
         if tensor is None or self.grid.next_rank is None:
             return
-        p = self.isend_forward(tensor)
+        p = self.isend_forward(tensor, doc_start)
         if p is not None:
             p.wait()
 
-    def recv_forward(self) -> Optional[torch.Tensor]:
+    def recv_forward(self):
+        """The hidden state, or (hidden, doc_start) with packing; None on the
+        first stage."""
         p = self.irecv_forward()
         return p.wait() if p is not None else None
 

@@ -97,11 +97,13 @@ class PipelineModule(nn.Module):
         raise IndexError(global_idx)
 
     # -- compute -----------------------------------------------------------
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, docs=None) -> torch.Tensor:
         """Run the local stage.  ``activation_checkpoint_interval`` groups
         layers and recomputes each group in backward (DeepSpeed semantics —
         trainer_base_ds_mp.py:428; interval 0 disables engine-level
-        checkpointing, leaving any per-layer flag to the layer itself)."""
+        checkpointing, leaving any per-layer flag to the layer itself).
+        ``docs`` (an ``ops.DocLayout`` of packed rows) goes to every decoder
+        layer, into the recompute as well; other layers ignore it."""
         interval = self.activation_checkpoint_interval
         if interval > 0 and self.training and torch.is_grad_enabled():
             i = 0
@@ -110,20 +112,21 @@ class PipelineModule(nn.Module):
                 group = self.layers[i : i + interval]
                 if any(p.requires_grad for layer in group for p in layer.parameters()):
                     x = torch.utils.checkpoint.checkpoint(
-                        self._run_group, i, i + len(group), x,
+                        self._run_group, i, i + len(group), x, docs,
                         use_reentrant=False, preserve_rng_state=False,
                     )
                 else:
-                    x = self._run_group(i, i + len(group), x)
+                    x = self._run_group(i, i + len(group), x, docs)
                 i += len(group)
             return x
-        for layer in self.layers:
-            x = layer(x)
-        return x
+        return self._run_group(0, len(self.layers), x, docs)
 
-    def _run_group(self, start: int, stop: int, x: torch.Tensor) -> torch.Tensor:
+    def _run_group(self, start: int, stop: int, x: torch.Tensor, docs=None) -> torch.Tensor:
         for layer in self.layers[start:stop]:
-            x = layer(x)
+            if docs is not None and getattr(layer, "takes_docs", False):
+                x = layer(x, docs=docs)
+            else:
+                x = layer(x)
         return x
 
     def extra_repr(self) -> str:

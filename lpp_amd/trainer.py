@@ -66,6 +66,9 @@ def build_dataset(cfg: TrainConfig):
     reference's Hydra dataset/collator instantiation
     (trainer_base_ds_mp.py:142-200,317).  Returns (dataset, collator)."""
     if cfg.data_kind == "synthetic":
+        if cfg.pack_sequences:
+            raise ValueError("pack_sequences needs data_kind=jsonl: synthetic rows are "
+                             "already full, there is nothing to pack")
         n = cfg.total_dataset_len or 4096
         ds = SyntheticCausalLMDataset(n, cfg.seq_len, cfg.model.vocab_size,
                                       seed=cfg.seed,
@@ -78,6 +81,14 @@ def build_dataset(cfg: TrainConfig):
             raise ValueError("data_kind=jsonl requires train_file")
         tok = build_tokenizer(cfg)
         ds = PromptResponseDataset(cfg.train_file)
+        if cfg.pack_sequences:
+            from torch.utils.data import default_collate
+
+            from .data import PackedRowsDataset
+
+            # items are finished [S] rows: the default collate stacks them
+            return PackedRowsDataset(ds, tok, cfg.seq_len, field=cfg.data_field), \
+                default_collate
         return ds, TextCollator(tok, cfg.seq_len, field=cfg.data_field)
     raise ValueError(f"unknown data_kind {cfg.data_kind!r} (synthetic | jsonl)")
 
