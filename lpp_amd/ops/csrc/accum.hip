@@ -35,14 +35,24 @@ __global__ __launch_bounds__(256) void accum_bf16_f32_kernel(
   if (t < (n - tail)) dst[tail + t] += __bfloat162float(src[tail + t]);
 }
 
+// One element per lane, for dst / src views that do not start on a 16-byte
+// boundary (a main_grad view behind a tensor of odd numel).
+__global__ __launch_bounds__(256) LPP_NO_PACKED_F32 void accum_bf16_f32_kernel_s(
+    float* __restrict__ dst, const __hip_bfloat16* __restrict__ src, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    dst[i] += __bfloat162float(src[i]);
+}
+
 void accum_bf16_f32(at::Tensor dst, at::Tensor src) {
   TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == at::kFloat && dst.is_contiguous());
   TORCH_CHECK(src.is_cuda() && src.scalar_type() == at::kBFloat16 && src.is_contiguous());
   TORCH_CHECK(dst.numel() == src.numel(), "accum: size mismatch");
   const int64_t n = dst.numel();
   const int grid = grid_for((n + 7) / 8, 256);
-  hipLaunchKernelGGL(accum_bf16_f32_kernel, dim3(grid), dim3(256), 0, current_stream(),
-                     dst.data_ptr<float>(),
+  auto kern = aligned(dst.data_ptr(), 16) && aligned(src.data_ptr(), 16)
+                  ? accum_bf16_f32_kernel
+                  : accum_bf16_f32_kernel_s;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, current_stream(), dst.data_ptr<float>(),
                      reinterpret_cast<const __hip_bfloat16*>(src.data_ptr()), n);
   LPP_CHECK_HIP(hipGetLastError());
 }

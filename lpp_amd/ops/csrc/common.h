@@ -126,6 +126,18 @@ __device__ __forceinline__ float block_reduce_max(float v, float* lds) {
     }                                                                       \
   }()
 
+// For kernels added as the one-element-per-lane side of a vector kernel: the
+// compiler must not pair their independent fp32 operations into packed
+// (two-lane) VALU instructions.
+#define LPP_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+
+// True when `p` may be cast to a Pack of `bytes` bytes.  Launchers take a
+// vector instantiation only when every pointer they cast passes this (and the
+// row pitch keeps later rows aligned); anything else runs the scalar one.
+static inline bool aligned(const void* p, size_t bytes) {
+  return reinterpret_cast<uintptr_t>(p) % bytes == 0;
+}
+
 static inline int grid_for(int64_t work_items, int block, int cap = 2048) {
   int64_t g = (work_items + block - 1) / block;
   return (int)std::min<int64_t>(g, cap);

@@ -118,10 +118,18 @@ std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits, at::Tensor labels) 
   const int grid = lpp::grid_for(n_rows, 1, 2048);
   LPP_DISPATCH_FLOAT(logits.scalar_type(), "ce_fwd", [&] {
     constexpr int VEC = 16 / sizeof(scalar_t);
-    hipLaunchKernelGGL((lpp::ce_fwd_kernel<scalar_t, VEC>), dim3(grid), dim3(lpp::CE_BLOCK),
-                       0, stream, (const scalar_t*)logits.data_ptr(),
-                       labels.data_ptr<int64_t>(), loss_sum.data_ptr<float>(),
-                       lse.data_ptr<float>(), count.data_ptr<int>(), n_rows, V);
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(lpp::CE_BLOCK), 0, stream,
+                         (const scalar_t*)logits.data_ptr(), labels.data_ptr<int64_t>(),
+                         loss_sum.data_ptr<float>(), lse.data_ptr<float>(),
+                         count.data_ptr<int>(), n_rows, V);
+    };
+    // 16-byte packets need an aligned base and a row pitch that keeps every
+    // row aligned; any other shape runs the one-element instantiation.
+    if (V % VEC == 0 && lpp::aligned(logits.data_ptr(), 16))
+      launch(lpp::ce_fwd_kernel<scalar_t, VEC>);
+    else
+      launch(lpp::ce_fwd_kernel<scalar_t, 1>);
   });
   LPP_CHECK_HIP(hipGetLastError());
   return {loss_sum, lse, count};
@@ -132,15 +140,26 @@ at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor labels, at::Tensor ls
   TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2);
   const int64_t n_rows = logits.size(0);
   const int V = logits.size(1);
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.is_contiguous() &&
+              labels.numel() == n_rows, "ce_bwd: labels must be [rows] int64 on GPU");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+              lse.numel() == n_rows, "ce_bwd: lse must be [rows] fp32 on GPU");
   auto dlogits = at::empty_like(logits);
   auto stream = lpp::current_stream();
   const int grid = lpp::grid_for(n_rows, 1, 2048);
   LPP_DISPATCH_FLOAT(logits.scalar_type(), "ce_bwd", [&] {
     constexpr int VEC = 16 / sizeof(scalar_t);
-    hipLaunchKernelGGL((lpp::ce_bwd_kernel<scalar_t, VEC>), dim3(grid), dim3(lpp::CE_BLOCK),
-                       0, stream, (const scalar_t*)logits.data_ptr(),
-                       labels.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                       (scalar_t*)dlogits.data_ptr(), (float)scale, n_rows, V);
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(lpp::CE_BLOCK), 0, stream,
+                         (const scalar_t*)logits.data_ptr(), labels.data_ptr<int64_t>(),
+                         lse.data_ptr<float>(), (scalar_t*)dlogits.data_ptr(), (float)scale,
+                         n_rows, V);
+    };
+    if (V % VEC == 0 && lpp::aligned(logits.data_ptr(), 16) &&
+        lpp::aligned(dlogits.data_ptr(), 16))
+      launch(lpp::ce_bwd_kernel<scalar_t, VEC>);
+    else
+      launch(lpp::ce_bwd_kernel<scalar_t, 1>);
   });
   LPP_CHECK_HIP(hipGetLastError());
   return dlogits;

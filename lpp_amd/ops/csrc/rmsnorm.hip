@@ -46,7 +46,7 @@ __global__ void rmsnorm_fwd_kernel(const T* __restrict__ x, const float* __restr
   }
 }
 
-// Scalar fallback for H not divisible by 16 bytes.
+// Scalar fallback for H not divisible by 16 bytes, or x / y not 16-byte aligned.
 template <typename T>
 __global__ void rmsnorm_fwd_kernel_s(const T* __restrict__ x, const float* __restrict__ w,
                                      T* __restrict__ y, float* __restrict__ invrms,
@@ -232,7 +232,7 @@ std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor weight, double eps)
   const int grid = lpp::grid_for(n_rows, 1, 4096);
   LPP_DISPATCH_FLOAT(x.scalar_type(), "rmsnorm_fwd", [&] {
     constexpr int VEC = 16 / sizeof(scalar_t);
-    if (H % VEC == 0) {
+    if (H % VEC == 0 && lpp::aligned(x.data_ptr(), 16) && lpp::aligned(y.data_ptr(), 16)) {
       hipLaunchKernelGGL((lpp::rmsnorm_fwd_kernel<scalar_t, VEC>), dim3(grid),
                          dim3(lpp::BLOCK), 0, stream, (const scalar_t*)x.data_ptr(),
                          w32.data_ptr<float>(), (scalar_t*)y.data_ptr(),
@@ -271,7 +271,11 @@ static std::vector<at::Tensor> rmsnorm_bwd_launch(const std::vector<at::Tensor>&
     const scalar_t* p2 = ndy >= 3 ? (const scalar_t*)dys[2].data_ptr() : p0;
     const scalar_t* pr = has_res ? (const scalar_t*)dres->data_ptr() : p0;
     const int n_it = H / (BLOCK * VEC);
-    const bool vec = VEC == 8 && H % (BLOCK * VEC) == 0 && n_it >= 1 && n_it <= 4;
+    // the vectorised kernel casts every operand to 16-byte packets
+    const bool al = aligned(p0, 16) && aligned(p1, 16) && aligned(p2, 16) && aligned(pr, 16) &&
+                    aligned(x.data_ptr(), 16) && aligned(dx.data_ptr(), 16) &&
+                    aligned(w32.data_ptr(), 16);
+    const bool vec = VEC == 8 && H % (BLOCK * VEC) == 0 && n_it >= 1 && n_it <= 4 && al;
     const int grid = grid_for(n_rows, 1, vec ? 2048 : 1024);
     auto partial = at::empty({grid, H}, x.options().dtype(at::kFloat));
     const size_t lds = vec ? 0 : (size_t)H * sizeof(float);
@@ -310,6 +314,8 @@ static std::vector<at::Tensor> rmsnorm_bwd_launch(const std::vector<at::Tensor>&
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor weight,
                                     at::Tensor invrms) {
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && x.is_contiguous());
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.sizes() == x.sizes(),
+              "rmsnorm_bwd: dy must match x (same dtype/shape)");
   return lpp::rmsnorm_bwd_launch({dy}, x, weight, invrms, c10::nullopt);
 }
 

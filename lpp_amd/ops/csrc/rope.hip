@@ -108,8 +108,14 @@ at::Tensor rope_launch(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, int64_t
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4, "rope: x must be [B,S,H,D]");
   const int B = x.size(0), S = x.size(1), H = x.size(2), D = x.size(3);
   TORCH_CHECK(D % 8 == 0, "rope: head_dim must be a multiple of 8");
-  TORCH_CHECK(cos_t.is_contiguous() && sin_t.is_contiguous());
-  TORCH_CHECK(cos_t.size(0) >= pos_offset + S, "rope cache too short");
+  TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda() && cos_t.is_contiguous() &&
+              sin_t.is_contiguous());
+  TORCH_CHECK(cos_t.scalar_type() == at::kFloat && sin_t.scalar_type() == at::kFloat);
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == D / 2 && sin_t.sizes() == cos_t.sizes(),
+              "rope: cos/sin must be [Smax, D/2]");
+  TORCH_CHECK(pos_offset >= 0 && cos_t.size(0) >= pos_offset + S, "rope cache too short");
+  TORCH_CHECK(lpp::aligned(x.data_ptr(), 4 * x.element_size()),
+              "rope: x must start on a 4-element boundary");
   auto y = at::empty_like(x);
   const int64_t total = (int64_t)B * S * H * (D / 8);
   auto stream = lpp::current_stream();
@@ -146,11 +152,13 @@ std::vector<at::Tensor> rope_bwd_t(at::Tensor dy, at::Tensor cos_t, at::Tensor s
   if (dy.scalar_type() != at::kBFloat16 || D != 128 || T == 0 || T % 64 != 0 ||
       T / 64 > 65535 || T > INT32_MAX || C > INT32_MAX)
     return {lpp::rope_launch<true>(dy, cos_t, sin_t, pos_offset)};
-  TORCH_CHECK(cos_t.is_contiguous() && sin_t.is_contiguous());
+  TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda() && cos_t.is_contiguous() &&
+              sin_t.is_contiguous());
   TORCH_CHECK(cos_t.scalar_type() == at::kFloat && sin_t.scalar_type() == at::kFloat);
   TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == D / 2 && sin_t.sizes() == cos_t.sizes(),
               "rope: cos/sin must be [Smax, D/2]");
   TORCH_CHECK(pos_offset >= 0 && cos_t.size(0) >= pos_offset + S, "rope cache too short");
+  TORCH_CHECK(lpp::aligned(dy.data_ptr(), 16), "rope: dy must be 16-byte aligned");
   auto dx = at::empty_like(dy);
   auto dxT = at::empty({C, T}, dy.options());
   dim3 grid((unsigned)H, (unsigned)(T / 64));

@@ -57,6 +57,39 @@ __global__ void swiglu_bwd_kernel(const T* __restrict__ dy, const T* __restrict_
   }
 }
 
+// One element per lane, the expressions of the two kernels above: ragged
+// numel, or a pointer that does not start on a 16-byte boundary.
+template <typename T>
+__global__ LPP_NO_PACKED_F32 void swiglu_fwd_kernel_s(const T* __restrict__ g,
+                                                      const T* __restrict__ u,
+                                                      T* __restrict__ y, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float gf = to_f32(g[i]);
+    float s = 1.f / (1.f + __expf(-gf));
+    y[i] = from_f32<T>(gf * s * to_f32(u[i]));
+  }
+}
+
+template <typename T>
+__global__ LPP_NO_PACKED_F32 void swiglu_bwd_kernel_s(const T* __restrict__ dy,
+                                                      const T* __restrict__ g,
+                                                      const T* __restrict__ u,
+                                                      T* __restrict__ dg, T* __restrict__ du,
+                                                      int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float d = to_f32(dy[i]);
+    float gf = to_f32(g[i]);
+    float uf = to_f32(u[i]);
+    float s = 1.f / (1.f + __expf(-gf));
+    float silu = gf * s;
+    float dsilu = s * (1.f + gf * (1.f - s));
+    dg[i] = from_f32<T>(d * uf * dsilu);
+    du[i] = from_f32<T>(d * silu);
+  }
+}
+
 // Tiled backward that also writes dg^T and du^T ([I, T]) for the wgrad GEMMs
 // of gate_proj / up_proj: one workgroup per 64-row x 128-column tile, the
 // arithmetic of swiglu_bwd_kernel line for line, natural b128 stores as
@@ -112,31 +145,48 @@ at::Tensor swiglu_fwd(at::Tensor gate, at::Tensor up) {
   auto stream = lpp::current_stream();
   LPP_DISPATCH_FLOAT(gate.scalar_type(), "swiglu_fwd", [&] {
     constexpr int VEC = 16 / sizeof(scalar_t);
-    TORCH_CHECK(n % VEC == 0, "swiglu: numel must be divisible by ", VEC);
-    const int64_t n_vec = n / VEC;
+    // ragged numel or a pointer off the 16-byte grid: one element per lane
+    const bool vec = n % VEC == 0 && lpp::aligned(gate.data_ptr(), 16) &&
+                     lpp::aligned(up.data_ptr(), 16) && lpp::aligned(y.data_ptr(), 16);
+    const int64_t n_vec = vec ? n / VEC : n;
     const int grid = lpp::grid_for(n_vec, 256);
-    hipLaunchKernelGGL((lpp::swiglu_fwd_kernel<scalar_t, VEC>), dim3(grid), dim3(256), 0,
-                       stream, (const scalar_t*)gate.data_ptr(),
-                       (const scalar_t*)up.data_ptr(), (scalar_t*)y.data_ptr(), n_vec);
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
+                         (const scalar_t*)gate.data_ptr(), (const scalar_t*)up.data_ptr(),
+                         (scalar_t*)y.data_ptr(), n_vec);
+    };
+    if (vec) launch(lpp::swiglu_fwd_kernel<scalar_t, VEC>);
+    else launch(lpp::swiglu_fwd_kernel_s<scalar_t>);
   });
   LPP_CHECK_HIP(hipGetLastError());
   return y;
 }
 
 std::vector<at::Tensor> swiglu_bwd(at::Tensor dy, at::Tensor gate, at::Tensor up) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous());
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && gate.is_contiguous() &&
+              up.is_contiguous());
+  TORCH_CHECK(dy.sizes() == gate.sizes() && gate.sizes() == up.sizes() &&
+              dy.scalar_type() == gate.scalar_type() &&
+              gate.scalar_type() == up.scalar_type());
   auto dg = at::empty_like(gate);
   auto du = at::empty_like(up);
   const int64_t n = gate.numel();
   auto stream = lpp::current_stream();
   LPP_DISPATCH_FLOAT(gate.scalar_type(), "swiglu_bwd", [&] {
     constexpr int VEC = 16 / sizeof(scalar_t);
-    const int64_t n_vec = n / VEC;
+    const bool vec = n % VEC == 0 && lpp::aligned(dy.data_ptr(), 16) &&
+                     lpp::aligned(gate.data_ptr(), 16) && lpp::aligned(up.data_ptr(), 16) &&
+                     lpp::aligned(dg.data_ptr(), 16) && lpp::aligned(du.data_ptr(), 16);
+    const int64_t n_vec = vec ? n / VEC : n;
     const int grid = lpp::grid_for(n_vec, 256);
-    hipLaunchKernelGGL((lpp::swiglu_bwd_kernel<scalar_t, VEC>), dim3(grid), dim3(256), 0,
-                       stream, (const scalar_t*)dy.data_ptr(),
-                       (const scalar_t*)gate.data_ptr(), (const scalar_t*)up.data_ptr(),
-                       (scalar_t*)dg.data_ptr(), (scalar_t*)du.data_ptr(), n_vec);
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
+                         (const scalar_t*)dy.data_ptr(), (const scalar_t*)gate.data_ptr(),
+                         (const scalar_t*)up.data_ptr(), (scalar_t*)dg.data_ptr(),
+                         (scalar_t*)du.data_ptr(), n_vec);
+    };
+    if (vec) launch(lpp::swiglu_bwd_kernel<scalar_t, VEC>);
+    else launch(lpp::swiglu_bwd_kernel_s<scalar_t>);
   });
   LPP_CHECK_HIP(hipGetLastError());
   return {dg, du};
