@@ -243,8 +243,22 @@ class LlamaAttention(nn.Module):
             # ragged single-token decode (continuous batching): every row
             # sits at its OWN position; RoPE phases gathered per row and
             # attention masked by per-row key validity.
-            assert S == 1, "ragged cache is a single-token decode contract"
             tick = getattr(cache, "tick", None)  # per-tick hoisted tensors
+            q_lens = getattr(tick, "q_lens", None)
+            assert S == 1 or q_lens is not None, (
+                "a ragged cache takes S > 1 only with per-tick pos and q_lens")
+            if q_lens is not None:
+                # ragged multi-token extend (chunked prefill): row n appends
+                # q_lens[n] tokens at its own position pos[n]; the gfx950
+                # kernels when supported, the fp32 reference otherwise.  A
+                # prefill tick whose longest chunk is one token (S == 1) comes
+                # here too: it carries no decode phases or mask
+                parent = getattr(cache, "parent", cache)
+                o = ops.extend_attention(
+                    q, k, v, parent.k, parent.v, cos, sin, tick.pos, q_lens=q_lens,
+                    rows=cache.rows if parent is not cache else None,
+                    lengths=parent.lengths, max_len=getattr(cache, "total_hint", None))
+                return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
             if ops.decode_attention_hip_supported(q, self.num_kv_heads):
                 # fused kernel on the parent cache tensors: RoPE, cache
                 # write and GQA attention in one launch - no gather, no
@@ -296,6 +310,14 @@ class LlamaAttention(nn.Module):
             o = ops.decode_attention(q, k, v, cache.k, cache.v, cos, sin, pos,
                                      max_len=pos + 1)
             cache.length = pos + 1
+            return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
+        if (S > 1 and pos > 0 and isinstance(cache, KVCache)
+                and ops.extend_attention_hip_supported(q, self.num_kv_heads)):
+            # uniform multi-token extend (a prompt fed in chunks): every row
+            # has `pos` tokens cached
+            o = ops.extend_attention(q, k, v, cache.k, cache.v, cos, sin, pos,
+                                     max_len=pos + S)
+            cache.length = pos + S
             return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
         q = ops.apply_rope(q, cos, sin, pos_offset=pos)
         k = ops.apply_rope(k, cos, sin, pos_offset=pos)

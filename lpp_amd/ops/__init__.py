@@ -99,7 +99,9 @@ from .rope import (build_rope_cache, apply_rope, apply_rope_positions,  # noqa: 
 from .swiglu import swiglu  # noqa: E402
 from .cross_entropy import shifted_cross_entropy  # noqa: E402
 from .attention import (DocLayout, causal_attention, decode_attention,  # noqa: E402
-                        decode_attention_ref, decode_attention_hip_supported)
+                        decode_attention_ref, decode_attention_hip_supported,
+                        extend_attention, extend_attention_ref,
+                        extend_attention_hip_supported)
 
 __all__ = [
     "rmsnorm",
@@ -116,6 +118,9 @@ __all__ = [
     "decode_attention",
     "decode_attention_ref",
     "decode_attention_hip_supported",
+    "extend_attention",
+    "extend_attention_ref",
+    "extend_attention_hip_supported",
     "extension",
     "use_hip",
     "force_eager",

@@ -290,3 +290,96 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
     return ext.attention_decode(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
                                 k_cache, v_cache, cos, sin, pos_t, rows, lengths,
                                 upos, int(max_len))
+
+
+# ---------------------------------------------------------------------------
+# Multi-token extend over a KV cache with per-row positions: decode's contract
+# with a time axis.
+#
+# Contract (both implementations): q [N,Sq,H,D], k_new/v_new [N,Sq,Hkv,D],
+# caches, cos/sin and rows as for decode.  Batch row n has positions[n] tokens
+# cached and q_lens[n] (default Sq) valid new tokens.  In place: token
+# i < q_lens[n] is rotated at positions[n] + i and its k/v land at
+# [row, positions[n] + i]; lengths[row] becomes positions[n] + q_lens[n].
+# Returns o [N,Sq,H,D]: o[n, i] attends keys 0 .. positions[n] + i of its
+# row; tokens i >= q_lens[n] write nothing and their output is zero.
+# ---------------------------------------------------------------------------
+
+def extend_attention_hip_supported(q: torch.Tensor, num_kv_heads: int) -> bool:
+    """True when ``extend_attention`` runs the gfx950 kernels for a query of
+    this device/dtype/geometry (else it runs the reference)."""
+    if not use_hip(q):
+        return False
+    if q.dtype is not torch.bfloat16 or q.shape[-1] != 128:
+        return False
+    H = q.shape[-2]
+    if num_kv_heads <= 0 or H % num_kv_heads or H // num_kv_heads not in _DECODE_REPS:
+        return False
+    return hasattr(extension(), "attention_extend")
+
+
+@torch.no_grad()
+def extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
+                         q_lens=None, rows=None, lengths=None, max_len=None) -> torch.Tensor:
+    """Plain per-row fp32 composition: rotate token i at p + i (the
+    apply_rope_positions formula), round to the cache dtype, write, softmax
+    over keys 0 .. p + i.  The CPU path and the oracle of the kernel;
+    ``max_len`` is unused."""
+    from .rope import apply_rope_positions
+
+    N, Sq, H, D = q.shape
+    rep = H // k_new.shape[2]
+    pos = _positions_tensor(positions, N, q.device).tolist()
+    lens = q_lens.tolist() if q_lens is not None else [Sq] * N
+    row_l = rows.tolist() if rows is not None else list(range(N))
+    scale = 1.0 / (D ** 0.5)
+    o = torch.zeros_like(q)
+    for n, (r, p, ln) in enumerate(zip(row_l, pos, lens)):
+        at = torch.arange(p, p + ln, device=q.device)
+        # the ln tokens of the row as a batch of single-token rows
+        qr = apply_rope_positions(q[n, :ln].unsqueeze(1), cos, sin, at)[:, 0]
+        kr = apply_rope_positions(k_new[n, :ln].unsqueeze(1), cos, sin, at)[:, 0]
+        k_cache[r, p : p + ln] = kr.to(k_cache.dtype)
+        v_cache[r, p : p + ln] = v_new[n, :ln].to(v_cache.dtype)
+        if lengths is not None:
+            lengths[r] = p + ln
+        kk = k_cache[r, : p + ln].float().repeat_interleave(rep, dim=1)  # [T,H,D]
+        vv = v_cache[r, : p + ln].float().repeat_interleave(rep, dim=1)
+        s = torch.einsum("ihd,thd->hit", qr.float(), kk) * scale
+        hidden = torch.arange(p + ln, device=q.device)[None, :] > at[:, None]  # [ln,T]
+        s = s.masked_fill(hidden[None], float("-inf"))
+        o[n, :ln] = torch.einsum("hit,thd->ihd", torch.softmax(s, dim=-1), vv).to(q.dtype)
+    return o
+
+
+@torch.no_grad()
+def extend_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
+                     q_lens=None, rows=None, lengths=None, max_len=None,
+                     chunk: int = 0, split: Optional[bool] = None) -> torch.Tensor:
+    """Fused RoPE + cache write + GQA attention of Sq new tokens per row over
+    the slot cache (an append launch, an MFMA attention launch and, on the
+    split path, a combine) for bf16 / head_dim 128 / H/Hkv in {1,2,4,8} on the
+    GPU; ``extend_attention_ref`` otherwise.  ``positions`` is a long tensor
+    [N] or an int (every row has that many tokens cached).  ``max_len`` is a
+    host bound on every position + q_len (default: the cache length).
+    ``chunk`` and ``split`` reach the kernel only: a key-chunk size from its
+    fixed set, and the split (True) or direct (False) path instead of the
+    choice by ``Sq * H/Hkv``."""
+    if not extend_attention_hip_supported(q, k_new.shape[2]):
+        return extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions,
+                                    q_lens=q_lens, rows=rows, lengths=lengths,
+                                    max_len=max_len)
+    ext = extension()
+    pos_t, upos = (None, positions) if isinstance(positions, int) else (positions, 0)
+    if lengths is not None:
+        # the append stores lengths[row]; the later launches still read the metadata
+        pos_t, q_lens, rows = (t.clone() if t is not None and _shares_storage(t, lengths)
+                               else t for t in (pos_t, q_lens, rows))
+    pos_t, q_lens, rows = (t.contiguous() if t is not None else None
+                           for t in (pos_t, q_lens, rows))
+    if max_len is None:
+        max_len = min(k_cache.shape[1], cos.shape[0])
+    return ext.attention_extend(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
+                                k_cache, v_cache, cos, sin, pos_t, q_lens, rows, lengths,
+                                upos, int(max_len), int(chunk),
+                                -1 if split is None else int(bool(split)))

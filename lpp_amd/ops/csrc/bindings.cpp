@@ -47,6 +47,13 @@ at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
                             int64_t max_len, int64_t chunk);
 int64_t attention_decode_chunk();
+at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
+                            at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
+                            at::Tensor sin_t, c10::optional<at::Tensor> positions,
+                            c10::optional<at::Tensor> q_lens, c10::optional<at::Tensor> rows,
+                            c10::optional<at::Tensor> lengths, int64_t uniform_pos,
+                            int64_t max_len, int64_t chunk, int64_t split);
+int64_t attention_extend_chunk(int64_t chunk);
 at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B);
 void wgrad_f32_accum(at::Tensor x, at::Tensor dy, at::Tensor dw);
 void wgrad_f32_accum_pre(at::Tensor xT, at::Tensor dyT, at::Tensor dw);
@@ -128,6 +135,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("chunk") = 0);
   m.def("attention_decode_chunk", &attention_decode_chunk,
         "keys per workgroup of attention_decode");
+  m.def("attention_extend", &attention_extend,
+        "multi-token extend: RoPE + KV-cache write of Sq new tokens per row at per-row "
+        "positions, GQA attention of token i over keys 0..p+i -> o [N,Sq,H,128]; chunk 0 = "
+        "the compiled-in chunk size, split -1 = by row count, 0 / 1 = direct / split path",
+        py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("cos"), py::arg("sin"), py::arg("positions"),
+        py::arg("q_lens"), py::arg("rows"), py::arg("lengths"), py::arg("uniform_pos"),
+        py::arg("max_len"), py::arg("chunk") = 0, py::arg("split") = -1);
+  m.def("attention_extend_chunk", &attention_extend_chunk,
+        "keys per split workgroup of attention_extend (chunk: 0 or a checked override)",
+        py::arg("chunk") = 0);
   m.def("wgrad_f32_accum", &wgrad_f32_accum, "dW_f32 += dY^T @ X (hipBLASLt, beta=1)");
   m.def("wgrad_f32_accum_pre", &wgrad_f32_accum_pre,
         "dW_f32 += dyT @ xT^T, pre-transposed k-contiguous operands (hipBLASLt, beta=1)");

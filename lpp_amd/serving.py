@@ -9,7 +9,9 @@ slot immediately, so short requests never wait for long ones (the
 attention is the ragged per-row-length branch of ``LlamaAttention``: for
 bf16 / head_dim 128 one fused gfx950 kernel per layer (``ops.decode_attention``
 - RoPE, cache write and GQA attention over each row's own prefix, read
-straight from the slot cache), eager SDPA otherwise.
+straight from the slot cache), eager SDPA otherwise.  With ``prefill_chunk``
+set, prompts of any lengths prefill together a chunk per tick through
+``ops.extend_attention`` while the active rows keep decoding.
 
 The reference has no inference capability at all (training-only template,
 SURVEY.md §0); this extends the framework's own ``generate``/
@@ -51,7 +53,17 @@ class Request:
 class ContinuousBatchingEngine:
     def __init__(self, model, max_slots: int, max_seq_len: int,
                  eos_token_id: Optional[int] = None,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None,
+                 prefill_chunk: Optional[int] = None):
+        """``prefill_chunk``: None admits as before (equal-length prompts
+        prefill together, each in one piece).  A value admits prompts of any
+        lengths together and prefills them at most that many tokens per row
+        per tick through ``ops.extend_attention``, while the rows already
+        decoding keep decoding every tick."""
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+        self.prefill_chunk = prefill_chunk
+        self.prefilling: Dict[int, list] = {}  # slot -> [request, prompt tokens cached]
         self.model = model
         self.model.eval()
         self.max_slots = max_slots
@@ -83,7 +95,7 @@ class ContinuousBatchingEngine:
         self.waiting.append(req)
 
     def pending(self) -> int:
-        return len(self.waiting) + len(self.active)
+        return len(self.waiting) + len(self.prefilling) + len(self.active)
 
     # ------------------------------------------------------------------
     def _run_layers(self, x: torch.Tensor, caches) -> torch.Tensor:
@@ -119,6 +131,51 @@ class ContinuousBatchingEngine:
                 self._last_logits[slot] = logits[i]
                 self.active[slot] = req
 
+    @torch.no_grad()
+    def _prefill_tick(self) -> None:
+        """Chunked admission: waiting requests of any prompt length take the
+        free slots, and every row still prefilling advances by at most
+        ``prefill_chunk`` tokens in ONE ragged extend forward (q_lens padded
+        to the longest chunk of the group).  A row whose prompt completes
+        becomes active; its first token is sampled from the logits of its
+        last prompt token."""
+        while self.waiting and self.free_slots:
+            req, slot = self.waiting.popleft(), self.free_slots.popleft()
+            for c in self.caches:
+                c.free(slot)
+            req.slot = slot
+            self.prefilling[slot] = [req, 0]
+        if not self.prefilling:
+            return
+        slots = sorted(self.prefilling)
+        done = [self.prefilling[s][1] for s in slots]
+        lens = [min(self.prefill_chunk, self.prefilling[s][0].prompt.numel() - d)
+                for s, d in zip(slots, done)]
+        ids = torch.zeros(len(slots), max(lens), dtype=torch.long)
+        for i, (s, d, n) in enumerate(zip(slots, done, lens)):
+            ids[i, :n] = self.prefilling[s][0].prompt.view(-1)[d : d + n]
+
+        class _Tick:
+            pass
+
+        tick = _Tick()
+        tick.pos = torch.tensor(done, dtype=torch.long, device=self.device)
+        tick.q_lens = torch.tensor(lens, dtype=torch.long, device=self.device)
+        slot_t = torch.tensor(slots, dtype=torch.long, device=self.device)
+        views = [GatherKVCache(c, slot_t, total_hint=max(d + n for d, n in zip(done, lens)))
+                 for c in self.caches]
+        for v in views:
+            v.tick = tick
+        logits = self._run_layers(ids.to(self.device), views)
+        for i, (s, d, n) in enumerate(zip(slots, done, lens)):
+            req = self.prefilling[s][0]
+            if d + n == req.prompt.numel():
+                del self.prefilling[s]
+                self._last_logits[s] = logits[i, n - 1]
+                self.active[s] = req
+            else:
+                self.prefilling[s][1] = d + n
+
     def _sample_batched(self, slots: List[int]) -> List[int]:
         """One device->host sync per tick (per-slot .item() calls dominated
         the first version's decode time)."""
@@ -143,7 +200,10 @@ class ContinuousBatchingEngine:
         """One engine tick: admit -> sample each active slot's pending
         logits (batched, one sync) -> retire finished -> ONE batched
         ragged decode for the rest.  Returns the uids finished this tick."""
-        self._admit()
+        if self.prefill_chunk is None:
+            self._admit()
+        else:
+            self._prefill_tick()
         done: List[str] = []
         slots = sorted(self.active)
         if not slots:

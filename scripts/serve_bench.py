@@ -33,6 +33,9 @@ def main() -> int:
     ap.add_argument("--slots", type=int, default=8)
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--max-seq", type=int, default=1024)
+    ap.add_argument("--prefill-chunk", type=int, default=None,
+                    help="chunked ragged prefill: at most this many prompt tokens per row "
+                         "per tick (default: whole-prompt admission)")
     args = ap.parse_args()
 
     assert torch.cuda.is_available(), "run on the GPU box"
@@ -47,7 +50,8 @@ def main() -> int:
     total_tokens = sum(lens)
 
     # ---- continuous batching: record per-request completion times
-    eng = ContinuousBatchingEngine(m, max_slots=args.slots, max_seq_len=args.max_seq)
+    eng = ContinuousBatchingEngine(m, max_slots=args.slots, max_seq_len=args.max_seq,
+                                   prefill_chunk=args.prefill_chunk)
     for i, (p, n) in enumerate(zip(prompts, lens)):
         eng.submit(Request(f"r{i}", p, n))
     finish_c = {}
@@ -81,6 +85,7 @@ def main() -> int:
                  for i in range(0, args.requests, args.slots)) - total_tokens
 
     print(f"requests={args.requests} slots={args.slots} prompt={args.prompt_len} "
+          f"prefill_chunk={args.prefill_chunk} "
           f"generated={total_tokens} tokens (mixed 16..256)")
     print(f"continuous: {t_cont:.2f} s = {total_tokens / t_cont:.0f} tok/s, "
           f"mean completion latency {lat_c:.2f} s")
