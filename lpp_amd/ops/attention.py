@@ -209,6 +209,10 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 # ---------------------------------------------------------------------------
 
 _DECODE_REPS = (1, 2, 4, 8)
+# decode alone also serves groups of 16 (attention_decode_mfma.hip); extend
+# stays at _DECODE_REPS and runs its reference there
+_DECODE_KERNEL_REPS = _DECODE_REPS + (16,)
+_DECODE_IMPLS = {None: 0, "valu": 1, "mfma": 2}
 
 
 def decode_attention_hip_supported(q: torch.Tensor, num_kv_heads: int) -> bool:
@@ -219,7 +223,7 @@ def decode_attention_hip_supported(q: torch.Tensor, num_kv_heads: int) -> bool:
     if q.dtype is not torch.bfloat16 or q.shape[-1] != 128:
         return False
     H = q.shape[-2]
-    if num_kv_heads <= 0 or H % num_kv_heads or H // num_kv_heads not in _DECODE_REPS:
+    if num_kv_heads <= 0 or H % num_kv_heads or H // num_kv_heads not in _DECODE_KERNEL_REPS:
         return False
     return hasattr(extension(), "attention_decode")
 
@@ -266,14 +270,25 @@ def _shares_storage(a: torch.Tensor, b: torch.Tensor) -> bool:
 
 @torch.no_grad()
 def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
-                     rows=None, lengths=None, max_len=None) -> torch.Tensor:
+                     rows=None, lengths=None, max_len=None,
+                     impl: Optional[str] = None) -> torch.Tensor:
     """Fused RoPE + cache write + GQA decode attention (one kernel launch plus
-    a small combine) for bf16 / head_dim 128 / H/Hkv in {1,2,4,8} on the GPU;
-    ``decode_attention_ref`` otherwise.  ``positions`` is a long tensor [N] or
-    an int (every row at that position).  ``max_len`` is a host bound on
-    every position + 1 (default: the cache length); a tighter bound launches
-    fewer workgroups."""
+    a small combine) for bf16 / head_dim 128 / H/Hkv in {1,2,4,8,16} on the
+    GPU; ``decode_attention_ref`` otherwise.  ``positions`` is a long tensor
+    [N] or an int (every row at that position).  ``max_len`` is a host bound
+    on every position + 1 (default: the cache length); a tighter bound launches
+    fewer workgroups.  ``impl`` names the kernel: ``"valu"`` (H/Hkv <= 8),
+    ``"mfma"`` (H/Hkv 8 or 16; an error for any other group size) or None for
+    the default of the group size (MFMA at 8 and 16, the vector-ALU kernel
+    below; profiles/README.md, Round 12).
+    The two differ in the last bits of o, never in what they write to the
+    cache."""
+    if impl not in _DECODE_IMPLS:
+        raise ValueError(f"decode_attention: impl must be None, 'valu' or 'mfma', got {impl!r}")
     if not decode_attention_hip_supported(q, k_new.shape[2]):
+        if impl is not None:
+            raise ValueError(f"decode_attention: impl={impl!r} needs the gfx950 kernel, which "
+                             "does not serve this device/dtype/geometry")
         return decode_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin,
                                     positions, rows=rows, lengths=lengths, max_len=max_len)
     ext = extension()
@@ -289,7 +304,7 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
         max_len = min(k_cache.shape[1], cos.shape[0])
     return ext.attention_decode(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
                                 k_cache, v_cache, cos, sin, pos_t, rows, lengths,
-                                upos, int(max_len))
+                                upos, int(max_len), 0, _DECODE_IMPLS[impl])
 
 
 # ---------------------------------------------------------------------------

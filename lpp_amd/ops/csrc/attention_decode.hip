@@ -26,16 +26,12 @@
 // of a row are never addressed (those > p hold stale data of earlier
 // requests), and the workgroup whose chunk holds p takes the new token from
 // the inputs.  That workgroup is also the one that stores it.
-#include "attention.h"
-#include "common.h"
+//
+// Groups of 8 and 16 heads have an MFMA kernel of their own
+// (attention_decode_mfma.hip); attention_decode.h holds what the two share.
+#include "attention_decode.h"
 
 namespace lpp {
-
-constexpr int kDecodeChunk = 256;   // C: keys per workgroup (profiles/README.md, Round 6)
-constexpr int kDecodeThreads = 256;
-constexpr int kDecodeWaves = kDecodeThreads / kWave;
-constexpr int kDecodeWs = ATTN_D + 4;  // fp32 partial: acc[128], m, l, pad to 16 B
-constexpr float kDecodeMinM = -1e30f;  // running max of an empty state (finite: no inf - inf)
 
 typedef __attribute__((__vector_size__(2 * sizeof(__bf16)))) __bf16 bf16x2_t;
 
@@ -63,29 +59,6 @@ __device__ __forceinline__ float row16_sum(float x) {
   x = dpp_add<0x4E>(x);   // quad_perm [2,3,0,1]
   x = dpp_add<0x141>(x);  // row_half_mirror
   return dpp_add<0x140>(x);  // row_mirror
-}
-
-__device__ __forceinline__ uint32_t bf16_bits(float x) {
-  return (uint32_t)__builtin_bit_cast(unsigned short, __float2bfloat16(x));
-}
-
-// Row metadata shared by both kernels.  A row whose cache row or position is
-// out of range is skipped (nothing read, nothing written, o = 0).
-struct DecodeRow {
-  int64_t r;
-  int p;
-  bool ok;
-};
-__device__ __forceinline__ DecodeRow decode_row(const int64_t* positions, const int64_t* rows,
-                                                int n, int uniform_pos, int slots,
-                                                int max_len) {
-  const int64_t p = positions ? positions[n] : (int64_t)uniform_pos;
-  const int64_t r = rows ? rows[n] : (int64_t)n;
-  DecodeRow d;
-  d.ok = r >= 0 && r < slots && p >= 0 && p < max_len;
-  d.r = r;
-  d.p = (int)p;
-  return d;
 }
 
 template <int REP, int C>
@@ -335,35 +308,6 @@ __global__ __launch_bounds__(kDecodeThreads, 2) void attn_decode_kernel(
   }
 }
 
-// o[n,h,:] = sum_j acc_j 2^(m_j - M) / sum_j l_j 2^(m_j - M) over the row's
-// ceil((p+1)/C) chunks, in chunk order.  One chunk takes the same path.
-template <int C>
-__global__ __launch_bounds__(ATTN_D) void attn_decode_combine_kernel(
-    const float* __restrict__ ws, const int64_t* __restrict__ positions,
-    const int64_t* __restrict__ rows, __hip_bfloat16* __restrict__ o, int uniform_pos,
-    int max_len, int slots, int H, int J) {
-  const int h = blockIdx.x, n = blockIdx.y, d = threadIdx.x;
-  const DecodeRow row = decode_row(positions, rows, n, uniform_pos, slots, max_len);
-  __hip_bfloat16* on = o + ((int64_t)n * H + h) * ATTN_D;
-  if (!row.ok) {
-    on[d] = __float2bfloat16(0.f);
-    return;
-  }
-  const int nj = row.p / C + 1;                // <= J: p < max_len <= J*C
-  const float* w = ws + ((int64_t)n * H + h) * J * kDecodeWs;
-  float mx = kDecodeMinM, lv = 0.f, a = 0.f;
-  for (int jj = 0; jj < nj; ++jj) {
-    const float* wj = w + (int64_t)jj * kDecodeWs;
-    const float mj = wj[ATTN_D];
-    const float mn = fmaxf(mx, mj);
-    const float f0 = exp2f(mx - mn), f1 = exp2f(mj - mn);
-    a = a * f0 + wj[d] * f1;
-    lv = lv * f0 + wj[ATTN_D + 1] * f1;
-    mx = mn;
-  }
-  on[d] = __float2bfloat16(a / lv);
-}
-
 template <int REP, int C>
 static void launch_decode(const at::Tensor& q, const at::Tensor& k_new, const at::Tensor& v_new,
                           at::Tensor& k_cache, at::Tensor& v_cache, const at::Tensor& cos_t,
@@ -384,10 +328,7 @@ static void launch_decode(const at::Tensor& q, const at::Tensor& k_new, const at
                      lengths, ws.data_ptr<float>(), uniform_pos, max_len, slots, Tmax, Hkv, J,
                      attn_scale().c);
   LPP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL((attn_decode_combine_kernel<C>), dim3(H, N), dim3(ATTN_D), 0, stream,
-                     ws.data_ptr<float>(), positions, rows, (__hip_bfloat16*)o.data_ptr(),
-                     uniform_pos, max_len, slots, H, J);
-  LPP_CHECK_HIP(hipGetLastError());
+  launch_decode_combine<C>(ws, positions, rows, o, uniform_pos, max_len, slots, N, H, J);
 }
 
 template <int C>
@@ -428,13 +369,17 @@ int64_t attention_decode_chunk() { return lpp::kDecodeChunk; }
 // chunk = 0: the compiled-in C.  128 / 256 / 512 select the other instantiations
 // for the chunk-size sweep (scripts/decode_bench.py); results differ in the
 // last bits between chunk sizes, never between calls of one size.
+// impl = 0: the kernel by group size (kDecodeMfmaDefault8), 1: the vector-ALU
+// kernel (H/Hkv <= 8), 2: the MFMA kernel (H/Hkv 8 or 16).  The choice never
+// depends on N or max_len: the two kernels differ in the last bits.
 at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
                             at::Tensor sin_t, c10::optional<at::Tensor> positions,
                             c10::optional<at::Tensor> rows,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                            int64_t max_len, int64_t chunk) {
+                            int64_t max_len, int64_t chunk, int64_t impl) {
   const char* who = "attention_decode";
+  TORCH_CHECK(impl >= 0 && impl <= 2, who, ": impl must be 0 (by geometry), 1 (valu) or 2 (mfma)");
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, who, ": bf16 CUDA q required");
   TORCH_CHECK(q.dim() == 4 && q.size(1) == 1 && q.size(3) == ATTN_D, who,
               ": q must be [N,1,H,128]");
@@ -497,7 +442,17 @@ at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
   int64_t* lp = lengths.has_value() ? lengths->data_ptr<int64_t>() : nullptr;
   const int rep = (int)(H / Hkv);
   if (chunk == 0) chunk = lpp::kDecodeChunk;
-#define LPP_DECODE_CHUNK(CC)                                                             \
+  TORCH_CHECK(chunk == 128 || chunk == 256 || chunk == 512, who,
+              ": chunk must be 0, 128, 256 or 512");
+  TORCH_CHECK(impl != 2 || rep == 8 || rep == 16, who,
+              ": the MFMA kernel serves H/Hkv 8 and 16, got ", rep);
+  TORCH_CHECK(impl != 1 || rep != 16, who, ": H/Hkv 16 has the MFMA kernel only");
+  if (impl == 2 || (impl == 0 && (rep == 16 || (rep == 8 && lpp::kDecodeMfmaDefault8)))) {
+    lpp::launch_decode_mfma(rep, (int)chunk, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t,
+                            pp, rp, lp, o, (int)uniform_pos, (int)max_len);
+    return o;
+  }
+#define LPP_DECODE_CHUNK(CC)                                                            \
   case CC:                                                                               \
     lpp::launch_decode_rep<CC>(rep, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t, pp, \
                                rp, lp, o, (int)uniform_pos, (int)max_len);               \

@@ -45,7 +45,7 @@ at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor sin_t, c10::optional<at::Tensor> positions,
                             c10::optional<at::Tensor> rows,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                            int64_t max_len, int64_t chunk);
+                            int64_t max_len, int64_t chunk, int64_t impl);
 int64_t attention_decode_chunk();
 at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
@@ -128,11 +128,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("doc_end") = py::none());
   m.def("attention_decode", &attention_decode,
         "fused single-token decode: RoPE + KV-cache write + GQA attention over keys 0..p of "
-        "each row's cache row -> o [N,1,H,128]; chunk 0 = the compiled-in chunk size",
+        "each row's cache row -> o [N,1,H,128]; chunk 0 = the compiled-in chunk size; impl 0 = "
+        "kernel by H/Hkv, 1 = vector ALU (H/Hkv <= 8), 2 = MFMA (H/Hkv 8 or 16)",
         py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("cos"), py::arg("sin"), py::arg("positions"),
         py::arg("rows"), py::arg("lengths"), py::arg("uniform_pos"), py::arg("max_len"),
-        py::arg("chunk") = 0);
+        py::arg("chunk") = 0, py::arg("impl") = 0);
   m.def("attention_decode_chunk", &attention_decode_chunk,
         "keys per workgroup of attention_decode");
   m.def("attention_extend", &attention_extend,

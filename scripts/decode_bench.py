@@ -4,13 +4,15 @@ sequence it replaces, one process, device events.
 Per point (geometry H/Hkv, batch N, mixed row lengths up to L):
   kernel  ops.decode_attention on the slot cache (kernel + combine), and the
           same op at the other compiled chunk sizes (the C sweep);
+  valu/mfma  (--impl both, H/Hkv = 8) the vector-ALU and the MFMA kernel named
+          explicitly, alternating in two passes - both passes are printed;
   model   the ragged branch of LlamaAttention.forward with the projections
           stubbed out, once on the kernel path and once under LPP_FORCE_EAGER
           (eager RoPE, two scatters, slice, repeat_interleave, masked SDPA).
 Prints microseconds per layer-step and the KV bytes/s they amount to, bytes
 from shapes: sum over rows of (p + 1) * Hkv * 128 * 2 B, for K and for V.
 
-    python scripts/decode_bench.py [--reps 200] [--quick]
+    python scripts/decode_bench.py [--reps 200] [--quick] [--impl valu|mfma|both]
 """
 
 from __future__ import annotations
@@ -54,7 +56,10 @@ def _time(fn, warmup, reps):
     return e0.elapsed_time(e1) * 1e3 / reps  # us per call
 
 
-def point(H, Hkv, N, L, reps, sweep):
+_IMPL = {"default": 0, "valu": 1, "mfma": 2}
+
+
+def point(H, Hkv, N, L, reps, sweep, impl="default"):
     dev = torch.device("cuda")
     g = torch.Generator(device=dev).manual_seed(0)
     pos_h = [L - 1] if N == 1 else [int(L // 4 + (L - 1 - L // 4) * i / (N - 1)) for i in range(N)]
@@ -71,14 +76,21 @@ def point(H, Hkv, N, L, reps, sweep):
     ext = ops.extension()
     out = {}
 
-    def op(chunk):
+    def op(chunk, which="default"):
         return lambda: ext.attention_decode(q, k, v, cache.k, cache.v, cos, sin, pos, None,
-                                            cache.lengths, 0, total, chunk)
+                                            cache.lengths, 0, total, chunk, _IMPL[which])
 
-    out["kernel"] = _time(op(0), 20, reps)
+    if impl == "both":
+        # the two kernels of a group of 8 in one process, alternating; a group
+        # of 16 has the MFMA kernel only
+        names = ("valu", "mfma") if H // Hkv == 8 else ("mfma",)
+        for name in names * 2:
+            out.setdefault(name, []).append(_time(op(0, name), 20, reps))
+        impl = "default"
+    out["kernel"] = _time(op(0, impl), 20, reps)
     if sweep:
         for c in (128, 256, 512):
-            out[f"C{c}"] = _time(op(c), 20, reps)
+            out[f"C{c}"] = _time(op(c, impl), 20, reps)
 
     # the model branch, projections stubbed
     cfg = ModelConfig(hidden_size=H * D, num_heads=H, num_kv_heads=Hkv, max_seq_len=L)
@@ -121,13 +133,20 @@ def point(H, Hkv, N, L, reps, sweep):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--quick", action="store_true", help="one geometry, no chunk sweep")
+    ap.add_argument("--quick", action="store_true",
+                    help="the GQA geometries (64/8, 128/8) only, no chunk sweep")
+    ap.add_argument("--impl", choices=["default", "valu", "mfma", "both"], default="default",
+                    help="kernel of the 'kernel' column (geometries it does not serve are "
+                         "left out); both: valu and mfma alternating, then the default")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs a GPU"
     C = ops.extension().attention_decode_chunk()
     print(f"# decode attention, bf16, D=128, compiled chunk C={C}, reps={args.reps}")
     print("# us per layer-step (TB/s of KV read in brackets)")
-    geoms = [(64, 8)] if args.quick else [(32, 32), (64, 64), (64, 8)]
+    geoms = [(64, 8), (128, 8)] if args.quick else [(32, 32), (64, 64), (64, 8), (128, 8)]
+    serves = {"default": (1, 2, 4, 8, 16), "both": (8, 16), "valu": (1, 2, 4, 8),
+              "mfma": (8, 16)}[args.impl]
+    geoms = [g for g in geoms if g[0] // g[1] in serves]
     hdr = f"{'H/Hkv':>7} {'N':>3} {'L':>5} {'KV MB':>8} | {'kernel':>15} {'model+kernel':>15} {'model eager':>15} {'x':>6}"
     if not args.quick:
         hdr += f" | {'C=128':>8} {'C=256':>8} {'C=512':>8}"
@@ -135,13 +154,17 @@ def main():
     for H, Hkv in geoms:
         for L in (512, 4096):
             for N in (1, 8, 32):
-                r, b = point(H, Hkv, N, L, args.reps, not args.quick)
+                r, b = point(H, Hkv, N, L, args.reps, not args.quick, args.impl)
                 f = lambda k: f"{r[k]:8.1f} ({b / r[k] * 1e-6:5.2f})"
                 line = (f"{H:>4}/{Hkv:<2} {N:>3} {L:>5} {b / 1e6:8.2f} | {f('kernel')} "
                         f"{f('model_kernel')} {f('model_eager')} "
                         f"{r['model_eager'] / r['model_kernel']:6.1f}")
                 if not args.quick:
                     line += " | " + " ".join(f"{r[k]:8.1f}" for k in ("C128", "C256", "C512"))
+                for name in ("valu", "mfma"):
+                    if name in r:
+                        line += f" | {name} " + " ".join(
+                            f"{t:7.1f} ({b / t * 1e-6:4.2f})" for t in r[name])
                 print(line, flush=True)
 
 
