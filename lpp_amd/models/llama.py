@@ -97,14 +97,29 @@ class RaggedKVCache:
     continuous batching (lpp_amd/serving.py): each slot holds an
     independent request at its own decode position.  ``per_row`` marks the
     ragged decode contract for LlamaAttention (per-row RoPE offsets +
-    key-validity mask).  Beyond the reference (training-only template)."""
+    key-validity mask).  Beyond the reference (training-only template).
+
+    ``kv_dtype=torch.float8_e4m3fn`` (opt-in) stores K and V as e4m3 bytes
+    with one power-of-two fp32 scale per (slot, kv head, token) in
+    ``k_scale`` / ``v_scale`` [slots, kv_heads, max_len]: half the bytes per
+    slot.  Such a cache is written and read through ``ops.decode_attention``
+    and ``ops.extend_attention`` only."""
 
     per_row = True
 
     def __init__(self, slots: int, max_len: int, kv_heads: int, head_dim: int,
-                 device, dtype):
-        self.k = torch.zeros(slots, max_len, kv_heads, head_dim, device=device, dtype=dtype)
+                 device, dtype, kv_dtype: Optional[torch.dtype] = None):
+        if kv_dtype not in (None, dtype, ops.FP8_KV_DTYPE):
+            raise ValueError(f"kv_dtype must be None, the model dtype or float8_e4m3fn, "
+                             f"got {kv_dtype}")
+        fp8 = kv_dtype is ops.FP8_KV_DTYPE
+        self.k = torch.zeros(slots, max_len, kv_heads, head_dim, device=device,
+                             dtype=kv_dtype or dtype)
         self.v = torch.zeros_like(self.k)
+        self.k_scale = self.v_scale = None
+        if fp8:
+            self.k_scale = torch.ones(slots, kv_heads, max_len, device=device)
+            self.v_scale = torch.ones_like(self.k_scale)
         self.lengths = torch.zeros(slots, dtype=torch.long, device=device)
 
     def slot_view(self, slot: int) -> SlotKVCache:
@@ -257,9 +272,14 @@ class LlamaAttention(nn.Module):
                 o = ops.extend_attention(
                     q, k, v, parent.k, parent.v, cos, sin, tick.pos, q_lens=q_lens,
                     rows=cache.rows if parent is not cache else None,
-                    lengths=parent.lengths, max_len=getattr(cache, "total_hint", None))
+                    lengths=parent.lengths, max_len=getattr(cache, "total_hint", None),
+                    k_scale=getattr(parent, "k_scale", None),
+                    v_scale=getattr(parent, "v_scale", None))
                 return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
-            if ops.decode_attention_hip_supported(q, self.num_kv_heads):
+            fp8 = getattr(getattr(cache, "parent", cache), "k_scale", None) is not None
+            # an fp8 cache has no eager branch: the op runs its reference where
+            # the kernel does not serve
+            if fp8 or ops.decode_attention_hip_supported(q, self.num_kv_heads):
                 # fused kernel on the parent cache tensors: RoPE, cache
                 # write and GQA attention in one launch - no gather, no
                 # repeat_interleave, no mask
@@ -270,7 +290,9 @@ class LlamaAttention(nn.Module):
                     pos if pos is not None else cache.lengths,
                     rows=cache.rows if parent is not cache else None,
                     lengths=parent.lengths,
-                    max_len=getattr(cache, "total_hint", None))
+                    max_len=getattr(cache, "total_hint", None),
+                    k_scale=getattr(parent, "k_scale", None),
+                    v_scale=getattr(parent, "v_scale", None))
                 return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
             if tick is not None:
                 q = ops.apply_rope_cs(q, tick.cos, tick.sin)

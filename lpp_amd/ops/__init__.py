@@ -101,7 +101,8 @@ from .cross_entropy import shifted_cross_entropy  # noqa: E402
 from .attention import (DocLayout, causal_attention, decode_attention,  # noqa: E402
                         decode_attention_ref, decode_attention_hip_supported,
                         extend_attention, extend_attention_ref,
-                        extend_attention_hip_supported)
+                        extend_attention_hip_supported, FP8_KV_DTYPE,
+                        quantize_kv_rows_fp8)
 
 __all__ = [
     "rmsnorm",
@@ -121,6 +122,8 @@ __all__ = [
     "extend_attention",
     "extend_attention_ref",
     "extend_attention_hip_supported",
+    "FP8_KV_DTYPE",
+    "quantize_kv_rows_fp8",
     "extension",
     "use_hip",
     "force_eager",

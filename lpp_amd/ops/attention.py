@@ -214,18 +214,79 @@ _DECODE_REPS = (1, 2, 4, 8)
 _DECODE_KERNEL_REPS = _DECODE_REPS + (16,)
 _DECODE_IMPLS = {None: 0, "valu": 1, "mfma": 2}
 
+# ---------------------------------------------------------------------------
+# FP8 KV cache (opt-in).  k_cache / v_cache are float8_e4m3fn
+# [slots,Tmax,Hkv,128]; k_scale / v_scale are fp32 [slots,Hkv,Tmax], one
+# power-of-two scale per (slot, kv head, token).  A stored row is the
+# round-to-nearest-even e4m3 of x / scale, and byte * scale is exact in bf16.
+# ---------------------------------------------------------------------------
+FP8_KV_DTYPE = torch.float8_e4m3fn
+_FP8_MIN_EXP = -100
 
-def decode_attention_hip_supported(q: torch.Tensor, num_kv_heads: int) -> bool:
+
+def quantize_kv_rows_fp8(x: torch.Tensor):
+    """Quantise rows [..., D] to (e4m3 [..., D], fp32 scale [...]).  With
+    ``amax = m * 2**E``, ``0.5 <= m < 1``: ``scale = 2**(E - 9)`` if
+    ``m <= 0.875`` else ``2**(E - 8)``, never below ``2**-100``, and 1 for a
+    row of zeros - so ``|x| / scale <= 448`` and nothing saturates."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    m, E = torch.frexp(amax)
+    e = torch.where(m <= 0.875, E - 9, E - 8).clamp(min=_FP8_MIN_EXP)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    return (xf / scale[..., None]).to(FP8_KV_DTYPE), scale
+
+
+def _check_fp8_args(who: str, k_cache, v_cache, k_scale, v_scale) -> bool:
+    """True for an fp8 cache (both scales required), False for any other."""
+    fp8 = k_cache.dtype is FP8_KV_DTYPE
+    if fp8 != (v_cache.dtype is FP8_KV_DTYPE):
+        raise ValueError(f"{who}: k_cache and v_cache must share a dtype")
+    if fp8 and (k_scale is None or v_scale is None):
+        raise ValueError(f"{who}: an fp8 cache needs k_scale and v_scale")
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError(f"{who}: k_scale / v_scale go with a float8_e4m3fn cache only")
+    return fp8
+
+
+def _cache_store(cache, scale, r, t, x):
+    """cache[r, t] = x ([.., Hkv, D]; r, t index tensors or an int and a
+    slice), quantised when the cache has a scale."""
+    if scale is None:
+        cache[r, t] = x.to(cache.dtype)
+        return
+    qb, sc = quantize_kv_rows_fp8(x)
+    cache.view(torch.uint8)[r, t] = qb.view(torch.uint8)   # bytes: fp8 has no index_put
+    if isinstance(t, slice):
+        scale[r, :, t] = sc.T          # [ln,Hkv] -> [Hkv,ln]
+    else:
+        scale[r, :, t] = sc            # advanced indices first: [N,Hkv]
+
+
+def _cache_prefix(cache, scale, r: int, T: int) -> torch.Tensor:
+    """fp32 [T,Hkv,D] of cache row r, dequantised when the cache has a scale."""
+    x = cache[r, :T].float()
+    return x if scale is None else x * scale[r, :, :T].T[..., None]
+
+
+def decode_attention_hip_supported(q: torch.Tensor, num_kv_heads: int,
+                                   cache_dtype: Optional[torch.dtype] = None) -> bool:
     """True when ``decode_attention`` runs the fused gfx950 kernel for a
-    query of this device/dtype/geometry (else it runs the reference)."""
+    query of this device/dtype/geometry (else it runs the reference).
+    ``cache_dtype``: None or bf16 for the bf16 cache, ``float8_e4m3fn`` for
+    the fp8 one."""
     if not use_hip(q):
+        return False
+    if cache_dtype not in (None, torch.bfloat16, FP8_KV_DTYPE):
         return False
     if q.dtype is not torch.bfloat16 or q.shape[-1] != 128:
         return False
     H = q.shape[-2]
     if num_kv_heads <= 0 or H % num_kv_heads or H // num_kv_heads not in _DECODE_KERNEL_REPS:
         return False
-    return hasattr(extension(), "attention_decode")
+    name = "attention_decode_fp8" if cache_dtype is FP8_KV_DTYPE else "attention_decode"
+    return hasattr(extension(), name)
 
 
 def _positions_tensor(positions, N: int, device) -> torch.Tensor:
@@ -236,11 +297,17 @@ def _positions_tensor(positions, N: int, device) -> torch.Tensor:
 
 @torch.no_grad()
 def decode_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
-                         rows=None, lengths=None, max_len=None) -> torch.Tensor:
+                         rows=None, lengths=None, max_len=None,
+                         k_scale=None, v_scale=None) -> torch.Tensor:
     """Plain per-row fp32 composition: rotate (the apply_rope_positions
     formula), round to the cache dtype, write, softmax over keys 0..p.
-    The CPU path and the oracle of the kernel; ``max_len`` is unused."""
+    The CPU path and the oracle of the kernel; ``max_len`` is unused.
+    With fp8 caches the rotated bf16 K row and the V row are quantised
+    (``quantize_kv_rows_fp8``), byte and scale are written, and the new token
+    is attended as its dequantised self, like every cached one."""
     from .rope import apply_rope_positions
+
+    _check_fp8_args("decode_attention_ref", k_cache, v_cache, k_scale, v_scale)
 
     N, _, H, D = q.shape
     Hkv = k_new.shape[2]
@@ -248,16 +315,16 @@ def decode_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions,
     pos = _positions_tensor(positions, N, q.device)
     row_t = rows if rows is not None else torch.arange(N, device=q.device)
     qr = apply_rope_positions(q, cos, sin, pos)
-    kr = apply_rope_positions(k_new, cos, sin, pos).to(k_cache.dtype)
-    k_cache[row_t, pos] = kr[:, 0]
-    v_cache[row_t, pos] = v_new[:, 0].to(v_cache.dtype)
+    kr = apply_rope_positions(k_new, cos, sin, pos)
+    _cache_store(k_cache, k_scale, row_t, pos, kr[:, 0])
+    _cache_store(v_cache, v_scale, row_t, pos, v_new[:, 0])
     if lengths is not None:
         lengths[row_t] = pos + 1
     scale = 1.0 / (D ** 0.5)
     o = torch.empty_like(q)
     for n, (r, p) in enumerate(zip(row_t.tolist(), pos.tolist())):
-        kk = k_cache[r, : p + 1].float().repeat_interleave(rep, dim=1)  # [T,H,D]
-        vv = v_cache[r, : p + 1].float().repeat_interleave(rep, dim=1)
+        kk = _cache_prefix(k_cache, k_scale, r, p + 1).repeat_interleave(rep, dim=1)  # [T,H,D]
+        vv = _cache_prefix(v_cache, v_scale, r, p + 1).repeat_interleave(rep, dim=1)
         s = torch.einsum("hd,thd->ht", qr[n, 0].float(), kk) * scale
         o[n, 0] = torch.einsum("ht,thd->hd", torch.softmax(s, dim=-1), vv).to(q.dtype)
     return o
@@ -271,7 +338,8 @@ def _shares_storage(a: torch.Tensor, b: torch.Tensor) -> bool:
 @torch.no_grad()
 def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
                      rows=None, lengths=None, max_len=None,
-                     impl: Optional[str] = None) -> torch.Tensor:
+                     impl: Optional[str] = None,
+                     k_scale=None, v_scale=None) -> torch.Tensor:
     """Fused RoPE + cache write + GQA decode attention (one kernel launch plus
     a small combine) for bf16 / head_dim 128 / H/Hkv in {1,2,4,8,16} on the
     GPU; ``decode_attention_ref`` otherwise.  ``positions`` is a long tensor
@@ -282,15 +350,25 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
     the default of the group size (MFMA at 8 and 16, the vector-ALU kernel
     below; profiles/README.md, Round 12).
     The two differ in the last bits of o, never in what they write to the
-    cache."""
+    cache.
+    The cache dtype picks the path.  ``float8_e4m3fn`` caches (opt-in) need
+    ``k_scale`` / ``v_scale``, fp32 [slots,Hkv,Tmax]: one power-of-two scale
+    per (slot, kv head, token), each row stored as the e4m3 of x / scale
+    (``quantize_kv_rows_fp8``).  They have one MFMA kernel for all five group
+    sizes, so ``impl`` must stay None."""
     if impl not in _DECODE_IMPLS:
         raise ValueError(f"decode_attention: impl must be None, 'valu' or 'mfma', got {impl!r}")
-    if not decode_attention_hip_supported(q, k_new.shape[2]):
+    fp8 = _check_fp8_args("decode_attention", k_cache, v_cache, k_scale, v_scale)
+    if fp8 and impl is not None:
+        raise ValueError("decode_attention: impl names a bf16-cache kernel; an fp8 cache "
+                         "takes impl=None")
+    if not decode_attention_hip_supported(q, k_new.shape[2], FP8_KV_DTYPE if fp8 else None):
         if impl is not None:
             raise ValueError(f"decode_attention: impl={impl!r} needs the gfx950 kernel, which "
                              "does not serve this device/dtype/geometry")
         return decode_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin,
-                                    positions, rows=rows, lengths=lengths, max_len=max_len)
+                                    positions, rows=rows, lengths=lengths, max_len=max_len,
+                                    k_scale=k_scale, v_scale=v_scale)
     ext = extension()
     pos_t, upos = (None, positions) if isinstance(positions, int) else (positions, 0)
     if pos_t is not None and lengths is not None and _shares_storage(pos_t, lengths):
@@ -302,6 +380,10 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
         rows = rows.contiguous()
     if max_len is None:
         max_len = min(k_cache.shape[1], cos.shape[0])
+    if fp8:
+        return ext.attention_decode_fp8(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
+                                        k_cache, v_cache, k_scale, v_scale, cos, sin, pos_t,
+                                        rows, lengths, upos, int(max_len), 0)
     return ext.attention_decode(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
                                 k_cache, v_cache, cos, sin, pos_t, rows, lengths,
                                 upos, int(max_len), 0, _DECODE_IMPLS[impl])
@@ -320,27 +402,35 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
 # row; tokens i >= q_lens[n] write nothing and their output is zero.
 # ---------------------------------------------------------------------------
 
-def extend_attention_hip_supported(q: torch.Tensor, num_kv_heads: int) -> bool:
+def extend_attention_hip_supported(q: torch.Tensor, num_kv_heads: int,
+                                   cache_dtype: Optional[torch.dtype] = None) -> bool:
     """True when ``extend_attention`` runs the gfx950 kernels for a query of
-    this device/dtype/geometry (else it runs the reference)."""
+    this device/dtype/geometry (else it runs the reference).  ``cache_dtype``
+    as for ``decode_attention_hip_supported``."""
     if not use_hip(q):
+        return False
+    if cache_dtype not in (None, torch.bfloat16, FP8_KV_DTYPE):
         return False
     if q.dtype is not torch.bfloat16 or q.shape[-1] != 128:
         return False
     H = q.shape[-2]
     if num_kv_heads <= 0 or H % num_kv_heads or H // num_kv_heads not in _DECODE_REPS:
         return False
-    return hasattr(extension(), "attention_extend")
+    name = "attention_extend_fp8" if cache_dtype is FP8_KV_DTYPE else "attention_extend"
+    return hasattr(extension(), name)
 
 
 @torch.no_grad()
 def extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
-                         q_lens=None, rows=None, lengths=None, max_len=None) -> torch.Tensor:
+                         q_lens=None, rows=None, lengths=None, max_len=None,
+                         k_scale=None, v_scale=None) -> torch.Tensor:
     """Plain per-row fp32 composition: rotate token i at p + i (the
     apply_rope_positions formula), round to the cache dtype, write, softmax
     over keys 0 .. p + i.  The CPU path and the oracle of the kernel;
-    ``max_len`` is unused."""
+    ``max_len`` is unused.  fp8 caches as in ``decode_attention_ref``."""
     from .rope import apply_rope_positions
+
+    _check_fp8_args("extend_attention_ref", k_cache, v_cache, k_scale, v_scale)
 
     N, Sq, H, D = q.shape
     rep = H // k_new.shape[2]
@@ -354,12 +444,12 @@ def extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions,
         # the ln tokens of the row as a batch of single-token rows
         qr = apply_rope_positions(q[n, :ln].unsqueeze(1), cos, sin, at)[:, 0]
         kr = apply_rope_positions(k_new[n, :ln].unsqueeze(1), cos, sin, at)[:, 0]
-        k_cache[r, p : p + ln] = kr.to(k_cache.dtype)
-        v_cache[r, p : p + ln] = v_new[n, :ln].to(v_cache.dtype)
+        _cache_store(k_cache, k_scale, r, slice(p, p + ln), kr)
+        _cache_store(v_cache, v_scale, r, slice(p, p + ln), v_new[n, :ln])
         if lengths is not None:
             lengths[r] = p + ln
-        kk = k_cache[r, : p + ln].float().repeat_interleave(rep, dim=1)  # [T,H,D]
-        vv = v_cache[r, : p + ln].float().repeat_interleave(rep, dim=1)
+        kk = _cache_prefix(k_cache, k_scale, r, p + ln).repeat_interleave(rep, dim=1)  # [T,H,D]
+        vv = _cache_prefix(v_cache, v_scale, r, p + ln).repeat_interleave(rep, dim=1)
         s = torch.einsum("ihd,thd->hit", qr.float(), kk) * scale
         hidden = torch.arange(p + ln, device=q.device)[None, :] > at[:, None]  # [ln,T]
         s = s.masked_fill(hidden[None], float("-inf"))
@@ -370,7 +460,8 @@ def extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions,
 @torch.no_grad()
 def extend_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
                      q_lens=None, rows=None, lengths=None, max_len=None,
-                     chunk: int = 0, split: Optional[bool] = None) -> torch.Tensor:
+                     chunk: int = 0, split: Optional[bool] = None,
+                     k_scale=None, v_scale=None) -> torch.Tensor:
     """Fused RoPE + cache write + GQA attention of Sq new tokens per row over
     the slot cache (an append launch, an MFMA attention launch and, on the
     split path, a combine) for bf16 / head_dim 128 / H/Hkv in {1,2,4,8} on the
@@ -379,11 +470,14 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
     host bound on every position + q_len (default: the cache length).
     ``chunk`` and ``split`` reach the kernel only: a key-chunk size from its
     fixed set, and the split (True) or direct (False) path instead of the
-    choice by ``Sq * H/Hkv``."""
-    if not extend_attention_hip_supported(q, k_new.shape[2]):
+    choice by ``Sq * H/Hkv``.  ``float8_e4m3fn`` caches with ``k_scale`` /
+    ``v_scale`` as for ``decode_attention``: the append quantises, the
+    attention kernel dequantises on its way into LDS."""
+    fp8 = _check_fp8_args("extend_attention", k_cache, v_cache, k_scale, v_scale)
+    if not extend_attention_hip_supported(q, k_new.shape[2], FP8_KV_DTYPE if fp8 else None):
         return extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions,
                                     q_lens=q_lens, rows=rows, lengths=lengths,
-                                    max_len=max_len)
+                                    max_len=max_len, k_scale=k_scale, v_scale=v_scale)
     ext = extension()
     pos_t, upos = (None, positions) if isinstance(positions, int) else (positions, 0)
     if lengths is not None:
@@ -394,6 +488,11 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
                            for t in (pos_t, q_lens, rows))
     if max_len is None:
         max_len = min(k_cache.shape[1], cos.shape[0])
+    if fp8:
+        return ext.attention_extend_fp8(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
+                                        k_cache, v_cache, k_scale, v_scale, cos, sin, pos_t,
+                                        q_lens, rows, lengths, upos, int(max_len), int(chunk),
+                                        -1 if split is None else int(bool(split)))
     return ext.attention_extend(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
                                 k_cache, v_cache, cos, sin, pos_t, q_lens, rows, lengths,
                                 upos, int(max_len), int(chunk),

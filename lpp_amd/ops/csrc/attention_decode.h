@@ -82,6 +82,39 @@ static void launch_decode_combine(const at::Tensor& ws, const int64_t* positions
   LPP_CHECK_HIP(hipGetLastError());
 }
 
+// ---- shared by the two MFMA kernels (attention_decode_mfma.hip, _fp8.hip) ----
+
+// max over the lanes l, l^16, l^32, l^48, in every lane.  Swapping a register
+// with itself leaves rows (0,0,2,2) and (1,1,3,3), then halves (lo,lo), (hi,hi).
+__device__ __forceinline__ float max_across_rows(float x) {
+  const int2v a = __builtin_amdgcn_permlane16_swap(as_i(x), as_i(x), false, false);
+  x = fmaxf(as_f(a[0]), as_f(a[1]));
+  const int2v b = __builtin_amdgcn_permlane32_swap(as_i(x), as_i(x), false, false);
+  return fmaxf(as_f(b[0]), as_f(b[1]));
+}
+__device__ __forceinline__ float sum_across_rows(float x) {
+  const int2v a = __builtin_amdgcn_permlane16_swap(as_i(x), as_i(x), false, false);
+  x = as_f(a[0]) + as_f(a[1]);
+  const int2v b = __builtin_amdgcn_permlane32_swap(as_i(x), as_i(x), false, false);
+  return as_f(b[0]) + as_f(b[1]);
+}
+
+// Byte offset of 16-byte chunk ch of staged key row r (32 rows of 256 bytes).
+__device__ __forceinline__ int vstage_off(int r, int ch) {
+  return 256 * r + 16 * (ch ^ ((r & 7) << 1));
+}
+
+constexpr int kMfmaStep = 32;                       // keys per wave step
+constexpr int kVStageBytes = kMfmaStep * ATTN_D * 2;  // one wave's V staging
+
+template <int REP>
+constexpr int decode_mfma_lds() {
+  // the 4-wave merge reuses the staging after the loop
+  constexpr int st = kDecodeWaves * REP * kDecodeWs * (int)sizeof(float);
+  constexpr int vs = kDecodeWaves * kVStageBytes;
+  return st > vs ? st : vs;
+}
+
 // The MFMA kernel's launch (attention_decode_mfma.hip): rep 8 or 16, chunk
 // 128 / 256 / 512; the arguments are the ones attention_decode() has checked.
 void launch_decode_mfma(int rep, int chunk, const at::Tensor& q, const at::Tensor& k_new,
@@ -89,5 +122,15 @@ void launch_decode_mfma(int rep, int chunk, const at::Tensor& q, const at::Tenso
                         const at::Tensor& cos_t, const at::Tensor& sin_t,
                         const int64_t* positions, const int64_t* rows, int64_t* lengths,
                         at::Tensor& o, int uniform_pos, int max_len);
+
+// The argument checks of attention_decode and attention_decode_fp8
+// (attention_decode.hip); with the scales given the caches must be e4m3.
+void decode_check_args(const char* who, const at::Tensor& q, const at::Tensor& k_new,
+                       const at::Tensor& v_new, const at::Tensor& k_cache,
+                       const at::Tensor& v_cache, const at::Tensor& cos_t,
+                       const at::Tensor& sin_t, const c10::optional<at::Tensor>& positions,
+                       const c10::optional<at::Tensor>& rows,
+                       const c10::optional<at::Tensor>& lengths, int64_t uniform_pos,
+                       int64_t max_len, const at::Tensor* k_scale, const at::Tensor* v_scale);
 
 }  // namespace lpp

@@ -360,26 +360,17 @@ static bool disjoint(const void* a, size_t na, const void* b, size_t nb) {
   return ca + na <= cb || cb + nb <= ca;
 }
 
-}  // namespace lpp
+// The argument checks of attention_decode and attention_decode_fp8.  The
+// caches are bf16, or e4m3 when the two scales ([slots,Hkv,Tmax] fp32) are given.
+void decode_check_args(const char* who, const at::Tensor& q, const at::Tensor& k_new,
+                       const at::Tensor& v_new, const at::Tensor& k_cache,
+                       const at::Tensor& v_cache, const at::Tensor& cos_t,
+                       const at::Tensor& sin_t, const c10::optional<at::Tensor>& positions,
+                       const c10::optional<at::Tensor>& rows,
+                       const c10::optional<at::Tensor>& lengths, int64_t uniform_pos,
+                       int64_t max_len, const at::Tensor* k_scale, const at::Tensor* v_scale) {
+  const at::ScalarType cache_t = k_scale ? at::kFloat8_e4m3fn : at::kBFloat16;
 
-using lpp::ATTN_D;
-
-int64_t attention_decode_chunk() { return lpp::kDecodeChunk; }
-
-// chunk = 0: the compiled-in C.  128 / 256 / 512 select the other instantiations
-// for the chunk-size sweep (scripts/decode_bench.py); results differ in the
-// last bits between chunk sizes, never between calls of one size.
-// impl = 0: the kernel by group size (kDecodeMfmaDefault8), 1: the vector-ALU
-// kernel (H/Hkv <= 8), 2: the MFMA kernel (H/Hkv 8 or 16).  The choice never
-// depends on N or max_len: the two kernels differ in the last bits.
-at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
-                            at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
-                            at::Tensor sin_t, c10::optional<at::Tensor> positions,
-                            c10::optional<at::Tensor> rows,
-                            c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                            int64_t max_len, int64_t chunk, int64_t impl) {
-  const char* who = "attention_decode";
-  TORCH_CHECK(impl >= 0 && impl <= 2, who, ": impl must be 0 (by geometry), 1 (valu) or 2 (mfma)");
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, who, ": bf16 CUDA q required");
   TORCH_CHECK(q.dim() == 4 && q.size(1) == 1 && q.size(3) == ATTN_D, who,
               ": q must be [N,1,H,128]");
@@ -393,9 +384,10 @@ at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                   v_cache.sizes() == k_cache.sizes(),
               who, ": caches must be [slots,Tmax,Hkv,128]");
   for (const at::Tensor* t : {&k_new, &v_new, &k_cache, &v_cache})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous() &&
-                    t->device() == q.device(),
-                who, ": k/v tensors must be contiguous bf16 on q's device");
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->device() == q.device() &&
+                    t->scalar_type() == (t == &k_cache || t == &v_cache ? cache_t : at::kBFloat16),
+                who, ": k/v tensors must be contiguous bf16",
+                k_scale ? " (the caches e4m3)" : "", " on q's device");
   TORCH_CHECK(q.is_contiguous(), who, ": q must be contiguous");
   for (const at::Tensor* t : {&cos_t, &sin_t})
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() &&
@@ -434,6 +426,46 @@ at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
   TORCH_CHECK(lpp::disjoint(k_cache.data_ptr(), k_cache.nbytes(), v_cache.data_ptr(),
                             v_cache.nbytes()),
               who, ": k_cache and v_cache must not alias");
+  if (!k_scale) return;
+  for (const at::Tensor* t : {k_scale, v_scale}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kFloat &&
+                    t->is_contiguous() && t->dim() == 3 && t->size(0) == slots &&
+                    t->size(1) == Hkv && t->size(2) == Tmax,
+                who, ": k_scale/v_scale must be contiguous fp32 [slots,Hkv,Tmax] on q's device");
+    // written by one workgroup while others read every other argument
+    std::vector<const at::Tensor*> others = {&q, &k_new, &v_new, &k_cache, &v_cache, &cos_t, &sin_t};
+    for (const c10::optional<at::Tensor>* o : {&positions, &rows, &lengths})
+      if (o->has_value()) others.push_back(&o->value());
+    if (t == v_scale) others.push_back(k_scale);
+    for (const at::Tensor* u : others)
+      TORCH_CHECK(lpp::disjoint(t->data_ptr(), t->nbytes(), u->data_ptr(), u->nbytes()), who,
+                  ": k_scale/v_scale must not alias another argument");
+  }
+}
+
+}  // namespace lpp
+
+using lpp::ATTN_D;
+
+int64_t attention_decode_chunk() { return lpp::kDecodeChunk; }
+
+// chunk = 0: the compiled-in C.  128 / 256 / 512 select the other instantiations
+// for the chunk-size sweep (scripts/decode_bench.py); results differ in the
+// last bits between chunk sizes, never between calls of one size.
+// impl = 0: the kernel by group size (kDecodeMfmaDefault8), 1: the vector-ALU
+// kernel (H/Hkv <= 8), 2: the MFMA kernel (H/Hkv 8 or 16).  The choice never
+// depends on N or max_len: the two kernels differ in the last bits.
+at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
+                            at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
+                            at::Tensor sin_t, c10::optional<at::Tensor> positions,
+                            c10::optional<at::Tensor> rows,
+                            c10::optional<at::Tensor> lengths, int64_t uniform_pos,
+                            int64_t max_len, int64_t chunk, int64_t impl) {
+  const char* who = "attention_decode";
+  TORCH_CHECK(impl >= 0 && impl <= 2, who, ": impl must be 0 (by geometry), 1 (valu) or 2 (mfma)");
+  lpp::decode_check_args(who, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t, positions, rows,
+                         lengths, uniform_pos, max_len, nullptr, nullptr);
+  const int64_t N = q.size(0), H = q.size(2), Hkv = k_new.size(2);
 
   auto o = at::empty_like(q);
   if (N == 0) return o;

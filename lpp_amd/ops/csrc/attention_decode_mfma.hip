@@ -55,37 +55,6 @@
 
 namespace lpp {
 
-// max over the lanes l, l^16, l^32, l^48, in every lane.  Swapping a register
-// with itself leaves rows (0,0,2,2) and (1,1,3,3), then halves (lo,lo), (hi,hi).
-__device__ __forceinline__ float max_across_rows(float x) {
-  const int2v a = __builtin_amdgcn_permlane16_swap(as_i(x), as_i(x), false, false);
-  x = fmaxf(as_f(a[0]), as_f(a[1]));
-  const int2v b = __builtin_amdgcn_permlane32_swap(as_i(x), as_i(x), false, false);
-  return fmaxf(as_f(b[0]), as_f(b[1]));
-}
-__device__ __forceinline__ float sum_across_rows(float x) {
-  const int2v a = __builtin_amdgcn_permlane16_swap(as_i(x), as_i(x), false, false);
-  x = as_f(a[0]) + as_f(a[1]);
-  const int2v b = __builtin_amdgcn_permlane32_swap(as_i(x), as_i(x), false, false);
-  return as_f(b[0]) + as_f(b[1]);
-}
-
-// Byte offset of 16-byte chunk ch of staged key row r (32 rows of 256 bytes).
-__device__ __forceinline__ int vstage_off(int r, int ch) {
-  return 256 * r + 16 * (ch ^ ((r & 7) << 1));
-}
-
-constexpr int kMfmaStep = 32;                       // keys per wave step
-constexpr int kVStageBytes = kMfmaStep * ATTN_D * 2;  // one wave's V staging
-
-template <int REP>
-constexpr int decode_mfma_lds() {
-  // the 4-wave merge reuses the staging after the loop
-  constexpr int st = kDecodeWaves * REP * kDecodeWs * (int)sizeof(float);
-  constexpr int vs = kDecodeWaves * kVStageBytes;
-  return st > vs ? st : vs;
-}
-
 template <int REP, int C>
 __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
     const __hip_bfloat16* __restrict__ q,      // [N,1,H,128]

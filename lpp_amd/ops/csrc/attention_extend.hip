@@ -42,7 +42,17 @@
 // row, so a batch row's output bits depend on its data, its position, its
 // q_len and the call's (Sq, REP) - not on N, the other rows, their order or
 // max_len.
+//
+// FP8 cache (attn_fp8.h: e4m3 rows, one power-of-two fp32 scale per (slot, kv
+// head, token) in k_scale / v_scale [slots,Hkv,Tmax]) is the template
+// parameter FP8 of the append and the attention kernel.  The append quantises:
+// the 8 lanes that hold a head's row agree on its amax, and the rotated bf16 K
+// row and the V row leave as 128 bytes and a scale.  The attention kernel
+// differs in ld_tile alone: 8 bytes and the key's scale become the bf16x8 that
+// write_tile stages, exactly, so the LDS images, the tile loop, the mask, the
+// split path and the combine are the bf16 ones.
 #include "attention.h"
+#include "attn_fp8.h"
 
 namespace lpp {
 
@@ -91,12 +101,18 @@ __device__ __forceinline__ unsigned short ae_bf16_bits(float x) {
 // partner: dims oct*8 .. +7 and 64 + oct*8 .. +7, two packets in, two out.
 // Tokens past a row's length (and skipped rows) leave the cache alone and zero
 // their q_rot, so the attention kernel never loads an uninitialised row.
+// FP8: the 8 lanes of a head (consecutive idx, so one iteration and one aligned
+// lane group) reduce the row's amax with three xor shuffles; V rows are work
+// items of the same loop, unrotated.
+template <bool FP8>
 __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_extend_append_kernel(
     const short* __restrict__ q,      // [N,Sq,H,128]
     const short* __restrict__ k_new,  // [N,Sq,Hkv,128]
     const short* __restrict__ v_new,
-    short* k_cache,                   // [slots,Tmax,Hkv,128]
-    short* v_cache,
+    std::conditional_t<FP8, uint8_t, short>* k_cache,  // [slots,Tmax,Hkv,128]
+    std::conditional_t<FP8, uint8_t, short>* v_cache,
+    float* k_scale,                   // [slots,Hkv,Tmax] (FP8)
+    float* v_scale,
     const float* __restrict__ cos_t,  // [Smax,64]
     const float* __restrict__ sin_t,
     const int64_t* __restrict__ positions, const int64_t* __restrict__ q_lens,
@@ -123,13 +139,48 @@ __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_e
   const float* cr = cos_t + (int64_t)pos * HALF;
   const float* sr = sin_t + (int64_t)pos * HALF;
 
-  for (int idx = tid; idx < (H + Hkv) * 8; idx += kExtendAppendThreads) {
+  // FP8: amax over the head's 8 lanes, this lane's two octets quantised and
+  // stored, the scale by one lane
+  [[maybe_unused]] auto store_row_fp8 = [&](const bf16x8& lo, const bf16x8& hi, auto* out,
+                                            float* scale, int oct) LPP_NO_PACKED_F32 {
+    float x[16], amax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      x[e] = bf16_to_f32(lo[e]);
+      x[8 + e] = bf16_to_f32(hi[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) amax = fmaxf(amax, fabsf(x[e]));
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+    const int ex = fp8_row_exp(amax);
+    const float inv = fp8_pow2(-ex);
+    uint32_t w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      w[e] = fp8_pack2(__fmul_rn(x[4 * e], inv), __fmul_rn(x[4 * e + 1], inv)) |
+             fp8_pack2(__fmul_rn(x[4 * e + 2], inv), __fmul_rn(x[4 * e + 3], inv)) << 16;
+    *reinterpret_cast<uint2*>(out + oct * 8) = make_uint2(w[0], w[1]);
+    *reinterpret_cast<uint2*>(out + HALF + oct * 8) = make_uint2(w[2], w[3]);
+    if (oct == 0) *scale = fp8_pow2(ex);
+  };
+
+  constexpr int KV_ITEMS = FP8 ? 2 : 1;            // FP8: V rows are items of this loop
+  for (int idx = tid; idx < (H + KV_ITEMS * Hkv) * 8; idx += kExtendAppendThreads) {
     const int head = idx >> 3, oct = idx & 7;
     const bool is_q = head < H;
-    const short* src = is_q ? qt + head * ATTN_D : kt + (head - H) * ATTN_D;
-    short* out = is_q ? qo + head * ATTN_D : k_cache + dst + (head - H) * ATTN_D;
+    const bool is_v = FP8 && head >= H + Hkv;
+    const int hk = head - H - (is_v ? Hkv : 0);    // kv head (!is_q)
+    const short* src = is_q ? qt + head * ATTN_D : (is_v ? vt : kt) + hk * ATTN_D;
     const bf16x8 lo = *reinterpret_cast<const bf16x8*>(src + oct * 8);
     const bf16x8 hi = *reinterpret_cast<const bf16x8*>(src + HALF + oct * 8);
+    [[maybe_unused]] const int64_t so = (row.r * Hkv + hk) * (int64_t)Tmax + pos;  // scale
+    if constexpr (FP8) {
+      if (is_v) {
+        store_row_fp8(lo, hi, v_cache + dst + hk * ATTN_D, v_scale + so, oct);
+        continue;
+      }
+    }
     float cs[8], sn[8];
     *reinterpret_cast<float4*>(&cs[0]) = *reinterpret_cast<const float4*>(cr + oct * 8);
     *reinterpret_cast<float4*>(&cs[4]) = *reinterpret_cast<const float4*>(cr + oct * 8 + 4);
@@ -142,22 +193,34 @@ __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_e
       olo[e] = (short)ae_bf16_bits(__fsub_rn(__fmul_rn(a, cs[e]), __fmul_rn(b, sn[e])));
       ohi[e] = (short)ae_bf16_bits(__fadd_rn(__fmul_rn(b, cs[e]), __fmul_rn(a, sn[e])));
     }
+    if constexpr (FP8) {
+      if (!is_q) {
+        store_row_fp8(olo, ohi, k_cache + dst + hk * ATTN_D, k_scale + so, oct);
+        continue;
+      }
+    }
+    short* out;
+    if constexpr (FP8) out = qo + head * ATTN_D;
+    else out = is_q ? qo + head * ATTN_D : k_cache + dst + hk * ATTN_D;
     *reinterpret_cast<bf16x8*>(out + oct * 8) = olo;
     *reinterpret_cast<bf16x8*>(out + HALF + oct * 8) = ohi;
   }
-  for (int idx = tid; idx < Hkv * (ATTN_D / 8); idx += kExtendAppendThreads)
-    reinterpret_cast<bf16x8*>(v_cache + dst)[idx] = reinterpret_cast<const bf16x8*>(vt)[idx];
+  if constexpr (!FP8)
+    for (int idx = tid; idx < Hkv * (ATTN_D / 8); idx += kExtendAppendThreads)
+      reinterpret_cast<bf16x8*>(v_cache + dst)[idx] = reinterpret_cast<const bf16x8*>(vt)[idx];
   if (lengths && i == 0 && tid == 0) lengths[row.r] = (int64_t)row.p + row.len;
 }
 
 // ---- attention ------------------------------------------------------------------
 // grid (row blocks, chunks (1 when !SPLIT), N * Hkv), 512 threads, heaviest
 // row block first.  2 waves/SIMD = one 512-thread workgroup per CU.
-template <int REP, bool SPLIT>
+template <int REP, bool SPLIT, bool FP8>
 __global__ __launch_bounds__(512, 2) LPP_NO_PACKED_F32 void attn_extend_kernel(
     const short* __restrict__ Qr,  // q_rot [N,Sq,H,128]
-    const short* __restrict__ Kc,  // [slots,Tmax,Hkv,128]
-    const short* __restrict__ Vc,
+    const std::conditional_t<FP8, uint8_t, short>* __restrict__ Kc,  // [slots,Tmax,Hkv,128]
+    const std::conditional_t<FP8, uint8_t, short>* __restrict__ Vc,
+    const float* __restrict__ Ks,  // [slots,Hkv,Tmax] (FP8)
+    const float* __restrict__ Vs,
     short* __restrict__ O,         // [N,Sq,H,128]             (!SPLIT)
     float* __restrict__ WsO,       // [N*Hkv,J,R,128] fp32     (SPLIT)
     float* __restrict__ WsML,      // [N*Hkv,J,R,2]: m, l      (SPLIT)
@@ -240,8 +303,17 @@ __global__ __launch_bounds__(512, 2) LPP_NO_PACKED_F32 void attn_extend_kernel(
   auto ld_tile = [&](int kv0, int pass, bf16x8& kreg, bf16x8& vreg) {
     const int key = min(kv0 + stage_row(wid, pass, st_r), kv_last);
     const int64_t rb = kv_base + (int64_t)key * sHkvD + st_c;
-    kreg = *reinterpret_cast<const bf16x8*>(&Kc[rb]);
-    vreg = *reinterpret_cast<const bf16x8*>(&Vc[rb]);
+    if constexpr (FP8) {
+      // the same 8 dims as 8 bytes, times the key's scale: exact in bf16
+      const int64_t so = (row.r * Hkv + hkv) * (int64_t)Tmax + key;
+      const uint2 kb = *reinterpret_cast<const uint2*>(&Kc[rb]);
+      const uint2 vb = *reinterpret_cast<const uint2*>(&Vc[rb]);
+      kreg = fp8x8_to_bf16(kb.x, kb.y, Ks[so]);
+      vreg = fp8x8_to_bf16(vb.x, vb.y, Vs[so]);
+    } else {
+      kreg = *reinterpret_cast<const bf16x8*>(&Kc[rb]);
+      vreg = *reinterpret_cast<const bf16x8*>(&Vc[rb]);
+    }
   };
   auto write_tile = [&](int buf, int /*kv0*/, int pass, bf16x8 kreg, bf16x8 vreg) {
     stage_chunk(k_lds(buf), st_off[pass], kreg);
@@ -428,15 +500,18 @@ __global__ __launch_bounds__(ATTN_D) LPP_NO_PACKED_F32 void attn_extend_combine_
 // waves would share one CU only at half the registers.
 // gfx950 (hipcc -O3): NumVgprs 204 for SPLIT=false at every REP, 206 (REP 1,
 // 2) and 207 (REP 4, 8) for SPLIT=true; all ScratchSize 0, 2 waves/SIMD, 64 KB
-// LDS.  Append 57 VGPRs, combine 12, no LDS, no scratch.  The three kernels
+// LDS, and the same figures for the FP8 instantiations (the conversion needs no
+// register the bf16 load did not hold).  Append 48 VGPRs (FP8: 65), combine 12,
+// no LDS, no scratch.  The three kernels
 // are LPP_NO_PACKED_F32: with packed fp32 the compiler pairs fp32 operations
 // into v_pk_* instructions (274 in this file) and takes 208 / 210 VGPRs
 // (append 58, combine 14) for the same arithmetic.  Nothing fails
 // with packed fp32 on; the figures of profiles/README.md, Round 11, are of
 // this machine code, and the packed form was not timed.
-template <int REP>
+template <int REP, bool FP8>
 static void launch_extend(const at::Tensor& q_rot, const at::Tensor& k_cache,
-                          const at::Tensor& v_cache, at::Tensor& o, const int64_t* positions,
+                          const at::Tensor& v_cache, const float* k_scale,
+                          const float* v_scale, at::Tensor& o, const int64_t* positions,
                           const int64_t* q_lens, const int64_t* rows, int uniform_pos,
                           int max_len, int C, bool split) {
   const int N = q_rot.size(0), Sq = q_rot.size(1), H = q_rot.size(2);
@@ -445,14 +520,15 @@ static void launch_extend(const at::Tensor& q_rot, const at::Tensor& k_cache,
   const int nblk = (R + AE_QB - 1) / AE_QB;
   auto stream = current_stream();
   const short* qp = (const short*)q_rot.data_ptr();
-  const short* kp = (const short*)k_cache.data_ptr();
-  const short* vp = (const short*)v_cache.data_ptr();
+  using cache_t = std::conditional_t<FP8, uint8_t, short>;
+  const cache_t* kp = (const cache_t*)k_cache.data_ptr();
+  const cache_t* vp = (const cache_t*)v_cache.data_ptr();
   const float c = attn_scale().c;
   if (!split) {
-    hipLaunchKernelGGL((attn_extend_kernel<REP, false>), dim3(nblk, 1, N * Hkv), dim3(512),
-                       AE_LDS_BYTES, stream, qp, kp, vp, (short*)o.data_ptr(), nullptr, nullptr,
-                       positions, q_lens, rows, uniform_pos, max_len, slots, Tmax, Sq, Hkv, 1,
-                       0, c);
+    hipLaunchKernelGGL((attn_extend_kernel<REP, false, FP8>), dim3(nblk, 1, N * Hkv),
+                       dim3(512), AE_LDS_BYTES, stream, qp, kp, vp, k_scale, v_scale,
+                       (short*)o.data_ptr(), nullptr, nullptr, positions, q_lens, rows,
+                       uniform_pos, max_len, slots, Tmax, Sq, Hkv, 1, 0, c);
     LPP_CHECK_HIP(hipGetLastError());
     return;
   }
@@ -460,10 +536,10 @@ static void launch_extend(const at::Tensor& q_rot, const at::Tensor& k_cache,
   TORCH_CHECK(J <= 65535, "attention_extend: too many key chunks");
   auto ws_o = at::empty({(int64_t)N * Hkv, J, R, ATTN_D}, q_rot.options().dtype(at::kFloat));
   auto ws_ml = at::empty({(int64_t)N * Hkv, J, R, 2}, q_rot.options().dtype(at::kFloat));
-  hipLaunchKernelGGL((attn_extend_kernel<REP, true>), dim3(nblk, J, N * Hkv), dim3(512),
-                     AE_LDS_BYTES, stream, qp, kp, vp, nullptr, ws_o.data_ptr<float>(),
-                     ws_ml.data_ptr<float>(), positions, q_lens, rows, uniform_pos, max_len,
-                     slots, Tmax, Sq, Hkv, J, C, c);
+  hipLaunchKernelGGL((attn_extend_kernel<REP, true, FP8>), dim3(nblk, J, N * Hkv), dim3(512),
+                     AE_LDS_BYTES, stream, qp, kp, vp, k_scale, v_scale, nullptr,
+                     ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), positions, q_lens, rows,
+                     uniform_pos, max_len, slots, Tmax, Sq, Hkv, J, C, c);
   LPP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(attn_extend_combine_kernel, dim3(R, N * Hkv), dim3(ATTN_D), 0, stream,
                      ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), positions, q_lens, rows,
@@ -485,24 +561,17 @@ static int64_t extend_chunk(int64_t chunk) {
   return chunk;
 }
 
-}  // namespace lpp
-
-using lpp::ATTN_D;
-
-// Keys per split workgroup: the compiled-in C (chunk = 0) or a checked override.
-int64_t attention_extend_chunk(int64_t chunk) { return lpp::extend_chunk(chunk); }
-
-// chunk: 0 = the compiled-in C, or one of 64 .. 1024 (tests, the C sweep of
-// scripts/extend_bench.py).  split: -1 = by the row count (Sq * H/Hkv below
-// kExtendSplitRows), 0 / 1 force the direct / the split path.  Results differ
-// in the last bits between chunk sizes and paths, never between calls of one.
-at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
-                            at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
-                            at::Tensor sin_t, c10::optional<at::Tensor> positions,
-                            c10::optional<at::Tensor> q_lens, c10::optional<at::Tensor> rows,
-                            c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                            int64_t max_len, int64_t chunk, int64_t split) {
-  const char* who = "attention_extend";
+// attention_extend (FP8 = false, no scales) and attention_extend_fp8.
+template <bool FP8>
+static at::Tensor extend(const char* who, const at::Tensor& q, const at::Tensor& k_new,
+                         const at::Tensor& v_new, at::Tensor& k_cache, at::Tensor& v_cache,
+                         at::Tensor* k_scale, at::Tensor* v_scale, const at::Tensor& cos_t,
+                         const at::Tensor& sin_t, const c10::optional<at::Tensor>& positions,
+                         const c10::optional<at::Tensor>& q_lens,
+                         const c10::optional<at::Tensor>& rows,
+                         const c10::optional<at::Tensor>& lengths, int64_t uniform_pos,
+                         int64_t max_len, int64_t chunk, int64_t split) {
+  using cache_t = std::conditional_t<FP8, uint8_t, short>;
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, who, ": bf16 CUDA q required");
   TORCH_CHECK(q.dim() == 4 && q.size(1) >= 1 && q.size(3) == ATTN_D, who,
               ": q must be [N,Sq,H,128]");
@@ -515,10 +584,14 @@ at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == Hkv && k_cache.size(3) == ATTN_D &&
                   v_cache.sizes() == k_cache.sizes(),
               who, ": caches must be [slots,Tmax,Hkv,128]");
-  for (const at::Tensor* t : {&k_new, &v_new, &k_cache, &v_cache})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->is_contiguous() &&
-                    t->device() == q.device(),
-                who, ": k/v tensors must be contiguous bf16 on q's device");
+  for (const at::Tensor* t : {&k_new, &v_new, (const at::Tensor*)&k_cache,
+                              (const at::Tensor*)&v_cache})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->device() == q.device() &&
+                    t->scalar_type() == (FP8 && (t == &k_cache || t == &v_cache)
+                                             ? at::kFloat8_e4m3fn
+                                             : at::kBFloat16),
+                who, ": k/v tensors must be contiguous bf16", FP8 ? " (the caches e4m3)" : "",
+                " on q's device");
   TORCH_CHECK(q.is_contiguous(), who, ": q must be contiguous");
   for (const at::Tensor* t : {&cos_t, &sin_t})
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() &&
@@ -564,6 +637,27 @@ at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
   TORCH_CHECK(lpp::extend_disjoint(k_cache.data_ptr(), k_cache.nbytes(), v_cache.data_ptr(),
                                    v_cache.nbytes()),
               who, ": k_cache and v_cache must not alias");
+  float* ksp = nullptr;
+  float* vsp = nullptr;
+  if constexpr (FP8) {
+    for (const at::Tensor* t : {k_scale, v_scale}) {
+      TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kFloat &&
+                      t->is_contiguous() && t->dim() == 3 && t->size(0) == slots &&
+                      t->size(1) == Hkv && t->size(2) == Tmax,
+                  who, ": k_scale/v_scale must be contiguous fp32 [slots,Hkv,Tmax] on q's device");
+      // written by the append while later launches read every other argument
+      std::vector<const at::Tensor*> others = {&q, &k_new, &v_new, &k_cache, &v_cache, &cos_t,
+                                               &sin_t};
+      for (const c10::optional<at::Tensor>* u : {&positions, &q_lens, &rows, &lengths})
+        if (u->has_value()) others.push_back(&u->value());
+      if (t == v_scale) others.push_back(k_scale);
+      for (const at::Tensor* u : others)
+        TORCH_CHECK(lpp::extend_disjoint(t->data_ptr(), t->nbytes(), u->data_ptr(), u->nbytes()),
+                    who, ": k_scale/v_scale must not alias another argument");
+    }
+    ksp = k_scale->data_ptr<float>();
+    vsp = v_scale->data_ptr<float>();
+  }
 
   auto o = at::empty_like(q);
   if (N == 0) return o;
@@ -576,11 +670,11 @@ at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
               ": H/Hkv must be 1, 2, 4 or 8, got ", rep);  // before the cache is written
 
   auto q_rot = at::empty_like(q);
-  hipLaunchKernelGGL(lpp::attn_extend_append_kernel, dim3((unsigned)Sq, (unsigned)N),
+  hipLaunchKernelGGL(lpp::attn_extend_append_kernel<FP8>, dim3((unsigned)Sq, (unsigned)N),
                      dim3(lpp::kExtendAppendThreads), 0, lpp::current_stream(),
                      (const short*)q.data_ptr(), (const short*)k_new.data_ptr(),
-                     (const short*)v_new.data_ptr(), (short*)k_cache.data_ptr(),
-                     (short*)v_cache.data_ptr(), cos_t.data_ptr<float>(),
+                     (const short*)v_new.data_ptr(), (cache_t*)k_cache.data_ptr(),
+                     (cache_t*)v_cache.data_ptr(), ksp, vsp, cos_t.data_ptr<float>(),
                      sin_t.data_ptr<float>(), pp, qp, rp, lp, (short*)q_rot.data_ptr(),
                      (int)uniform_pos, (int)max_len, (int)slots, (int)Tmax, (int)Sq, (int)H,
                      (int)Hkv);
@@ -589,8 +683,8 @@ at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
   const bool do_split = split < 0 ? Sq * rep < lpp::kExtendSplitRows : split == 1;
 #define LPP_EXTEND_REP(RR)                                                                  \
   case RR:                                                                                  \
-    lpp::launch_extend<RR>(q_rot, k_cache, v_cache, o, pp, qp, rp, (int)uniform_pos,        \
-                           (int)max_len, (int)C, do_split);                                 \
+    lpp::launch_extend<RR, FP8>(q_rot, k_cache, v_cache, ksp, vsp, o, pp, qp, rp,           \
+                                (int)uniform_pos, (int)max_len, (int)C, do_split);          \
     break
   switch (rep) {
     LPP_EXTEND_REP(1);
@@ -602,4 +696,40 @@ at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
   }
 #undef LPP_EXTEND_REP
   return o;
+}
+
+}  // namespace lpp
+
+using lpp::ATTN_D;
+
+// Keys per split workgroup: the compiled-in C (chunk = 0) or a checked override.
+int64_t attention_extend_chunk(int64_t chunk) { return lpp::extend_chunk(chunk); }
+
+// chunk: 0 = the compiled-in C, or one of 64 .. 1024 (tests, the C sweep of
+// scripts/extend_bench.py).  split: -1 = by the row count (Sq * H/Hkv below
+// kExtendSplitRows), 0 / 1 force the direct / the split path.  Results differ
+// in the last bits between chunk sizes and paths, never between calls of one.
+at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
+                            at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
+                            at::Tensor sin_t, c10::optional<at::Tensor> positions,
+                            c10::optional<at::Tensor> q_lens, c10::optional<at::Tensor> rows,
+                            c10::optional<at::Tensor> lengths, int64_t uniform_pos,
+                            int64_t max_len, int64_t chunk, int64_t split) {
+  return lpp::extend<false>("attention_extend", q, k_new, v_new, k_cache, v_cache, nullptr,
+                            nullptr, cos_t, sin_t, positions, q_lens, rows, lengths, uniform_pos,
+                            max_len, chunk, split);
+}
+
+// The same over e4m3 caches with per-(slot, kv head, token) scales.
+at::Tensor attention_extend_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
+                                at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale,
+                                at::Tensor v_scale, at::Tensor cos_t, at::Tensor sin_t,
+                                c10::optional<at::Tensor> positions,
+                                c10::optional<at::Tensor> q_lens,
+                                c10::optional<at::Tensor> rows,
+                                c10::optional<at::Tensor> lengths, int64_t uniform_pos,
+                                int64_t max_len, int64_t chunk, int64_t split) {
+  return lpp::extend<true>("attention_extend_fp8", q, k_new, v_new, k_cache, v_cache, &k_scale,
+                           &v_scale, cos_t, sin_t, positions, q_lens, rows, lengths, uniform_pos,
+                           max_len, chunk, split);
 }

@@ -46,6 +46,13 @@ at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             c10::optional<at::Tensor> rows,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
                             int64_t max_len, int64_t chunk, int64_t impl);
+at::Tensor attention_decode_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
+                                at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale,
+                                at::Tensor v_scale, at::Tensor cos_t, at::Tensor sin_t,
+                                c10::optional<at::Tensor> positions,
+                                c10::optional<at::Tensor> rows,
+                                c10::optional<at::Tensor> lengths, int64_t uniform_pos,
+                                int64_t max_len, int64_t chunk);
 int64_t attention_decode_chunk();
 at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
@@ -53,6 +60,14 @@ at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             c10::optional<at::Tensor> q_lens, c10::optional<at::Tensor> rows,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
                             int64_t max_len, int64_t chunk, int64_t split);
+at::Tensor attention_extend_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
+                                at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale,
+                                at::Tensor v_scale, at::Tensor cos_t, at::Tensor sin_t,
+                                c10::optional<at::Tensor> positions,
+                                c10::optional<at::Tensor> q_lens,
+                                c10::optional<at::Tensor> rows,
+                                c10::optional<at::Tensor> lengths, int64_t uniform_pos,
+                                int64_t max_len, int64_t chunk, int64_t split);
 int64_t attention_extend_chunk(int64_t chunk);
 at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B);
 void wgrad_f32_accum(at::Tensor x, at::Tensor dy, at::Tensor dw);
@@ -134,6 +149,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v_cache"), py::arg("cos"), py::arg("sin"), py::arg("positions"),
         py::arg("rows"), py::arg("lengths"), py::arg("uniform_pos"), py::arg("max_len"),
         py::arg("chunk") = 0, py::arg("impl") = 0);
+  m.def("attention_decode_fp8", &attention_decode_fp8,
+        "attention_decode over e4m3 caches [slots,Tmax,Hkv,128] with power-of-two fp32 scales "
+        "k_scale / v_scale [slots,Hkv,Tmax]; one MFMA kernel for H/Hkv 1, 2, 4, 8 and 16",
+        py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cos"),
+        py::arg("sin"), py::arg("positions"), py::arg("rows"), py::arg("lengths"),
+        py::arg("uniform_pos"), py::arg("max_len"), py::arg("chunk") = 0);
   m.def("attention_decode_chunk", &attention_decode_chunk,
         "keys per workgroup of attention_decode");
   m.def("attention_extend", &attention_extend,
@@ -144,6 +166,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v_cache"), py::arg("cos"), py::arg("sin"), py::arg("positions"),
         py::arg("q_lens"), py::arg("rows"), py::arg("lengths"), py::arg("uniform_pos"),
         py::arg("max_len"), py::arg("chunk") = 0, py::arg("split") = -1);
+  m.def("attention_extend_fp8", &attention_extend_fp8,
+        "attention_extend over e4m3 caches with k_scale / v_scale as for attention_decode_fp8: "
+        "the append quantises each K and V row, the attention kernel dequantises into LDS",
+        py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cos"),
+        py::arg("sin"), py::arg("positions"), py::arg("q_lens"), py::arg("rows"),
+        py::arg("lengths"), py::arg("uniform_pos"), py::arg("max_len"), py::arg("chunk") = 0,
+        py::arg("split") = -1);
   m.def("attention_extend_chunk", &attention_extend_chunk,
         "keys per split workgroup of attention_extend (chunk: 0 or a checked override)",
         py::arg("chunk") = 0);

@@ -54,14 +54,24 @@ class ContinuousBatchingEngine:
     def __init__(self, model, max_slots: int, max_seq_len: int,
                  eos_token_id: Optional[int] = None,
                  generator: Optional[torch.Generator] = None,
-                 prefill_chunk: Optional[int] = None):
+                 prefill_chunk: Optional[int] = None,
+                 kv_dtype: Optional[torch.dtype] = None):
         """``prefill_chunk``: None admits as before (equal-length prompts
         prefill together, each in one piece).  A value admits prompts of any
         lengths together and prefills them at most that many tokens per row
         per tick through ``ops.extend_attention``, while the rows already
-        decoding keep decoding every tick."""
+        decoding keep decoding every tick.
+
+        ``kv_dtype``: None keeps the cache in the model dtype.
+        ``torch.float8_e4m3fn`` (opt-in) halves its bytes: e4m3 rows with one
+        power-of-two scale per (slot, kv head, token), see ``RaggedKVCache``.
+        It needs ``prefill_chunk``, because the one-piece admission writes the
+        cache without quantising."""
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+        if kv_dtype is torch.float8_e4m3fn and prefill_chunk is None:
+            raise ValueError("an fp8 KV cache needs prefill_chunk: only the chunked prefill "
+                             "(ops.extend_attention) quantises what it appends")
         self.prefill_chunk = prefill_chunk
         self.prefilling: Dict[int, list] = {}  # slot -> [request, prompt tokens cached]
         self.model = model
@@ -76,7 +86,7 @@ class ContinuousBatchingEngine:
         self.decoders = [l for l in model.layers if isinstance(l, DecoderLayerPipe)]
         self.caches = [
             RaggedKVCache(max_slots, max_seq_len, cfg.kv_heads, cfg.head_dim,
-                          self.device, p.dtype)
+                          self.device, p.dtype, kv_dtype=kv_dtype)
             for _ in self.decoders
         ]
         self.free_slots = deque(range(max_slots))

@@ -11,8 +11,12 @@ Per point (geometry H/Hkv, batch N, mixed row lengths up to L):
           (eager RoPE, two scatters, slice, repeat_interleave, masked SDPA).
 Prints microseconds per layer-step and the KV bytes/s they amount to, bytes
 from shapes: sum over rows of (p + 1) * Hkv * 128 * 2 B, for K and for V.
+--kv-dtype fp8 runs the e4m3 cache instead (attention_decode_fp8.hip, one kernel
+for every group size, so no --impl): (p + 1) * Hkv * (128 + 4) B per cache, the
+4 being the row's scale; that cache has no eager branch to compare with.
 
     python scripts/decode_bench.py [--reps 200] [--quick] [--impl valu|mfma|both]
+                                   [--kv-dtype bf16|fp8]
 """
 
 from __future__ import annotations
@@ -59,24 +63,33 @@ def _time(fn, warmup, reps):
 _IMPL = {"default": 0, "valu": 1, "mfma": 2}
 
 
-def point(H, Hkv, N, L, reps, sweep, impl="default"):
+def point(H, Hkv, N, L, reps, sweep, impl="default", fp8=False):
     dev = torch.device("cuda")
     g = torch.Generator(device=dev).manual_seed(0)
     pos_h = [L - 1] if N == 1 else [int(L // 4 + (L - 1 - L // 4) * i / (N - 1)) for i in range(N)]
     total = max(pos_h) + 1
-    cache = RaggedKVCache(N, L, Hkv, D, dev, torch.bfloat16)
-    cache.k.copy_(torch.randn(cache.k.shape, generator=g, device=dev))
-    cache.v.copy_(torch.randn(cache.v.shape, generator=g, device=dev))
+    cache = RaggedKVCache(N, L, Hkv, D, dev, torch.bfloat16,
+                          kv_dtype=ops.FP8_KV_DTYPE if fp8 else None)
+    for dst, scale in ((cache.k, cache.k_scale), (cache.v, cache.v_scale)):
+        x = torch.randn(dst.shape, generator=g, device=dev).bfloat16()
+        if fp8:
+            x, sc = ops.quantize_kv_rows_fp8(x)
+            scale.copy_(sc.transpose(1, 2))
+        dst.copy_(x)
     pos = torch.tensor(pos_h, device=dev)
     q = torch.randn(N, 1, H, D, generator=g, device=dev).bfloat16()
     k = torch.randn(N, 1, Hkv, D, generator=g, device=dev).bfloat16()
     v = torch.randn(N, 1, Hkv, D, generator=g, device=dev).bfloat16()
     cos, sin = ops.build_rope_cache(L, D, 10000.0, dev)
-    kv_bytes = sum(p + 1 for p in pos_h) * Hkv * D * 2 * 2
+    kv_bytes = sum(p + 1 for p in pos_h) * Hkv * ((D + 4) if fp8 else D * 2) * 2
     ext = ops.extension()
     out = {}
 
     def op(chunk, which="default"):
+        if fp8:
+            return lambda: ext.attention_decode_fp8(q, k, v, cache.k, cache.v, cache.k_scale,
+                                                    cache.v_scale, cos, sin, pos, None,
+                                                    cache.lengths, 0, total, chunk)
         return lambda: ext.attention_decode(q, k, v, cache.k, cache.v, cos, sin, pos, None,
                                             cache.lengths, 0, total, chunk, _IMPL[which])
 
@@ -122,6 +135,9 @@ def point(H, Hkv, N, L, reps, sweep, impl="default"):
 
     t_copy = _time(copy_only, 20, reps)
     out["model_kernel"] = _time(branch, 20, reps) - t_copy
+    if fp8:
+        out["model_eager"] = float("nan")
+        return out, kv_bytes
     os.environ["LPP_FORCE_EAGER"] = "1"
     try:
         out["model_eager"] = _time(branch, 20, reps) - t_copy
@@ -138,10 +154,15 @@ def main():
     ap.add_argument("--impl", choices=["default", "valu", "mfma", "both"], default="default",
                     help="kernel of the 'kernel' column (geometries it does not serve are "
                          "left out); both: valu and mfma alternating, then the default")
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the e4m3 cache and its kernel (with --impl default only)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs a GPU"
+    fp8 = args.kv_dtype == "fp8"
+    assert not fp8 or args.impl == "default", "the fp8 cache has one kernel: no --impl"
     C = ops.extension().attention_decode_chunk()
-    print(f"# decode attention, bf16, D=128, compiled chunk C={C}, reps={args.reps}")
+    print(f"# decode attention, {args.kv_dtype} cache, D=128, compiled chunk C={C}, "
+          f"reps={args.reps}")
     print("# us per layer-step (TB/s of KV read in brackets)")
     geoms = [(64, 8), (128, 8)] if args.quick else [(32, 32), (64, 64), (64, 8), (128, 8)]
     serves = {"default": (1, 2, 4, 8, 16), "both": (8, 16), "valu": (1, 2, 4, 8),
@@ -154,7 +175,7 @@ def main():
     for H, Hkv in geoms:
         for L in (512, 4096):
             for N in (1, 8, 32):
-                r, b = point(H, Hkv, N, L, args.reps, not args.quick, args.impl)
+                r, b = point(H, Hkv, N, L, args.reps, not args.quick, args.impl, fp8)
                 f = lambda k: f"{r[k]:8.1f} ({b / r[k] * 1e-6:5.2f})"
                 line = (f"{H:>4}/{Hkv:<2} {N:>3} {L:>5} {b / 1e6:8.2f} | {f('kernel')} "
                         f"{f('model_kernel')} {f('model_eager')} "

@@ -12,7 +12,10 @@ Prints microseconds per layer-step and executed TF/s, operations from shapes:
 4 * 128 * H * sum over rows and tokens of (p + i + 1).
 Yardstick: (1, 4096, 0) against causal_attention's forward kernel.
 
-    python scripts/extend_bench.py [--reps 50] [--quick | --sweep]
+--kv-dtype fp8 runs the kernels over the e4m3 cache (the append quantises, the
+attention kernel dequantises into LDS); that cache has no eager branch.
+
+    python scripts/extend_bench.py [--reps 50] [--quick | --sweep] [--kv-dtype bf16|fp8]
 """
 
 from __future__ import annotations
@@ -67,6 +70,9 @@ def _flops(N, Sq, p):
     return 4 * D * H * N * sum(p + i + 1 for i in range(Sq))
 
 
+FP8 = False  # --kv-dtype fp8
+
+
 def _inputs(N, Sq, p):
     dev = torch.device("cuda")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -75,6 +81,11 @@ def _inputs(N, Sq, p):
     cache = KVCache(N, L, HKV, D, dev, torch.bfloat16)
     cache.k.copy_(rn(*cache.k.shape))
     cache.v.copy_(rn(*cache.v.shape))
+    cache.scales = {}
+    if FP8:
+        (cache.k, ks), (cache.v, vs) = (ops.quantize_kv_rows_fp8(t) for t in (cache.k, cache.v))
+        cache.scales = dict(k_scale=ks.transpose(1, 2).contiguous(),
+                            v_scale=vs.transpose(1, 2).contiguous())
     cos, sin = ops.build_rope_cache(L, D, 10000.0, dev)
     return cache, rn(N, Sq, H, D), rn(N, Sq, HKV, D), rn(N, Sq, HKV, D), cos, sin, L
 
@@ -85,14 +96,16 @@ def point(N, Sq, p, reps, sweep, eager=True):
 
     def op(chunk, split):
         return lambda: ops.extend_attention(q, k, v, cache.k, cache.v, cos, sin, p,
-                                            max_len=L, chunk=chunk, split=split)
+                                            max_len=L, chunk=chunk, split=split,
+                                            **cache.scales)
 
     out["kernel"] = _time(op(0, None), 10, reps)
     if sweep:
         out["direct"] = _time(op(0, False), 10, reps)
         for c in CHUNKS:
             out[f"C{c}"] = _time(op(c, True), 10, reps)
-    if not eager:
+    if not eager or FP8:
+        out["eager"] = float("nan")
         return out
 
     cfg = ModelConfig(hidden_size=H * D, num_heads=H, num_kv_heads=HKV, max_seq_len=L)
@@ -121,7 +134,7 @@ def yardstick(reps):
     cache, q, k, v, cos, sin, L = _inputs(N, Sq, 0)
     ext = ops.extension()
     t_ext = _time(lambda: ops.extend_attention(q, k, v, cache.k, cache.v, cos, sin, 0,
-                                               max_len=L), 10, reps)
+                                               max_len=L, **cache.scales), 10, reps)
     t_fwd = _time(lambda: ext.attention_fwd(q, k, v), 10, reps)
     f = _flops(N, Sq, 0)
     print(f"# yardstick (1, 4096, 0): extend (RoPE + append + attention) {t_ext:9.1f} us "
@@ -135,10 +148,13 @@ def main():
     ap.add_argument("--quick", action="store_true", help="no path / chunk sweep")
     ap.add_argument("--sweep", action="store_true",
                     help="the threshold / C sweep points instead: the op alone, every path")
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "extend_bench needs a GPU"
+    global FP8
+    FP8 = args.kv_dtype == "fp8"
     C = ops.extension().attention_extend_chunk()
-    print(f"# extend attention, bf16, D=128, H/Hkv {H}/{HKV}, compiled chunk C={C}, "
+    print(f"# extend attention, {args.kv_dtype} cache, D=128, H/Hkv {H}/{HKV}, compiled chunk C={C}, "
           f"reps={args.reps}")
     if args.sweep:
         print(f"# us, the op alone | {'N':>3} {'Sq':>5} {'p':>5} {'R':>5} | {'kernel':>9} "

@@ -36,6 +36,8 @@ def main() -> int:
     ap.add_argument("--prefill-chunk", type=int, default=None,
                     help="chunked ragged prefill: at most this many prompt tokens per row "
                          "per tick (default: whole-prompt admission)")
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the e4m3 KV cache (needs --prefill-chunk)")
     args = ap.parse_args()
 
     assert torch.cuda.is_available(), "run on the GPU box"
@@ -51,7 +53,9 @@ def main() -> int:
 
     # ---- continuous batching: record per-request completion times
     eng = ContinuousBatchingEngine(m, max_slots=args.slots, max_seq_len=args.max_seq,
-                                   prefill_chunk=args.prefill_chunk)
+                                   prefill_chunk=args.prefill_chunk,
+                                   kv_dtype=torch.float8_e4m3fn if args.kv_dtype == "fp8"
+                                   else None)
     for i, (p, n) in enumerate(zip(prompts, lens)):
         eng.submit(Request(f"r{i}", p, n))
     finish_c = {}
@@ -85,7 +89,7 @@ def main() -> int:
                  for i in range(0, args.requests, args.slots)) - total_tokens
 
     print(f"requests={args.requests} slots={args.slots} prompt={args.prompt_len} "
-          f"prefill_chunk={args.prefill_chunk} "
+          f"prefill_chunk={args.prefill_chunk} kv_dtype={args.kv_dtype} "
           f"generated={total_tokens} tokens (mixed 16..256)")
     print(f"continuous: {t_cont:.2f} s = {total_tokens / t_cont:.0f} tok/s, "
           f"mean completion latency {lat_c:.2f} s")
