@@ -103,24 +103,45 @@ class RaggedKVCache:
     with one power-of-two fp32 scale per (slot, kv head, token) in
     ``k_scale`` / ``v_scale`` [slots, kv_heads, max_len]: half the bytes per
     slot.  Such a cache is written and read through ``ops.decode_attention``
-    and ``ops.extend_attention`` only."""
+    and ``ops.extend_attention`` only.
+
+    ``page_size`` (opt-in, with ``num_pages``) makes the cache paged: ``k`` /
+    ``v`` are a pool [num_pages, page_size, kv_heads, head_dim] (scales
+    [num_pages, kv_heads, page_size]) and ``block_table`` int32 [slots,
+    ceil(max_len / page_size)] names the pages of each slot, so a slot takes
+    pages for the tokens it will hold, not ``max_len`` of them.  Who owns
+    which page is the caller's business (``ContinuousBatchingEngine`` keeps
+    the free list).  Like fp8, a paged cache is written and read through the
+    two ops only; the kernels serve ``page_size`` 64."""
 
     per_row = True
 
     def __init__(self, slots: int, max_len: int, kv_heads: int, head_dim: int,
-                 device, dtype, kv_dtype: Optional[torch.dtype] = None):
+                 device, dtype, kv_dtype: Optional[torch.dtype] = None,
+                 page_size: Optional[int] = None, num_pages: Optional[int] = None):
         if kv_dtype not in (None, dtype, ops.FP8_KV_DTYPE):
             raise ValueError(f"kv_dtype must be None, the model dtype or float8_e4m3fn, "
                              f"got {kv_dtype}")
+        if (page_size is None) != (num_pages is None):
+            raise ValueError("page_size and num_pages go together")
+        if page_size is not None and (page_size < 1 or num_pages < 1):
+            raise ValueError(f"page_size and num_pages must be >= 1, got {page_size}, "
+                             f"{num_pages}")
         fp8 = kv_dtype is ops.FP8_KV_DTYPE
-        self.k = torch.zeros(slots, max_len, kv_heads, head_dim, device=device,
+        # the pool keeps the slot cache's rank: [rows, tokens per row, Hkv, D]
+        n_rows, row_len = (slots, max_len) if page_size is None else (num_pages, page_size)
+        self.k = torch.zeros(n_rows, row_len, kv_heads, head_dim, device=device,
                              dtype=kv_dtype or dtype)
         self.v = torch.zeros_like(self.k)
         self.k_scale = self.v_scale = None
         if fp8:
-            self.k_scale = torch.ones(slots, kv_heads, max_len, device=device)
+            self.k_scale = torch.ones(n_rows, kv_heads, row_len, device=device)
             self.v_scale = torch.ones_like(self.k_scale)
         self.lengths = torch.zeros(slots, dtype=torch.long, device=device)
+        self.block_table = None
+        if page_size is not None:
+            self.block_table = torch.zeros(slots, -(-max_len // page_size), dtype=torch.int32,
+                                           device=device)
 
     def slot_view(self, slot: int) -> SlotKVCache:
         return SlotKVCache(self, slot)
@@ -274,12 +295,14 @@ class LlamaAttention(nn.Module):
                     rows=cache.rows if parent is not cache else None,
                     lengths=parent.lengths, max_len=getattr(cache, "total_hint", None),
                     k_scale=getattr(parent, "k_scale", None),
-                    v_scale=getattr(parent, "v_scale", None))
+                    v_scale=getattr(parent, "v_scale", None),
+                    block_table=getattr(parent, "block_table", None))
                 return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
             fp8 = getattr(getattr(cache, "parent", cache), "k_scale", None) is not None
-            # an fp8 cache has no eager branch: the op runs its reference where
-            # the kernel does not serve
-            if fp8 or ops.decode_attention_hip_supported(q, self.num_kv_heads):
+            paged = getattr(getattr(cache, "parent", cache), "block_table", None) is not None
+            # an fp8 or paged cache has no eager branch: the op runs its
+            # reference where the kernel does not serve
+            if fp8 or paged or ops.decode_attention_hip_supported(q, self.num_kv_heads):
                 # fused kernel on the parent cache tensors: RoPE, cache
                 # write and GQA attention in one launch - no gather, no
                 # repeat_interleave, no mask
@@ -292,7 +315,8 @@ class LlamaAttention(nn.Module):
                     lengths=parent.lengths,
                     max_len=getattr(cache, "total_hint", None),
                     k_scale=getattr(parent, "k_scale", None),
-                    v_scale=getattr(parent, "v_scale", None))
+                    v_scale=getattr(parent, "v_scale", None),
+                    block_table=getattr(parent, "block_table", None))
                 return self.o_proj(o.reshape(B, S, self.num_heads * self.head_dim))
             if tick is not None:
                 q = ops.apply_rope_cs(q, tick.cos, tick.sin)

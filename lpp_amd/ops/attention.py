@@ -270,13 +270,67 @@ def _cache_prefix(cache, scale, r: int, T: int) -> torch.Tensor:
     return x if scale is None else x * scale[r, :, :T].T[..., None]
 
 
+# ---------------------------------------------------------------------------
+# Paged KV cache (opt-in).  With ``block_table`` (int32 [table_rows,
+# max_pages]) k_cache / v_cache are a pool [num_pages, page, Hkv, D] (scales
+# [num_pages, Hkv, page]) and token t of table row r lives at
+# cache[block_table[r, t // page], t % page]; ``rows`` selects table rows and
+# ``lengths`` is [table_rows].  The kernels serve page == 64.
+# ---------------------------------------------------------------------------
+PAGE_TOKENS = 64
+
+
+def _check_block_table(who: str, block_table, k_cache) -> None:
+    if block_table.dim() != 2 or block_table.dtype is not torch.int32:
+        raise ValueError(f"{who}: block_table must be int32 [table_rows, max_pages], got "
+                         f"{block_table.dtype} {tuple(block_table.shape)}")
+    if block_table.device != k_cache.device:
+        raise ValueError(f"{who}: block_table on {block_table.device}, the cache on "
+                         f"{k_cache.device}")
+
+
+def _gather_pages(cache, scale, block_table):
+    """The slot-layout copy of a pool: cache [table_rows, max_pages * page, Hkv,
+    D] and scale [table_rows, Hkv, max_pages * page] (or None).  Ids outside
+    the pool (entries no token uses) are clamped."""
+    bt = block_table.long().clamp(0, cache.shape[0] - 1)
+    R, M = bt.shape
+    P, Hkv = cache.shape[1], cache.shape[2]
+    slot = cache.view(torch.uint8)[bt].reshape(R, M * P, Hkv, -1).view(cache.dtype)
+    if scale is None:
+        return slot, None
+    return slot, scale[bt].permute(0, 2, 1, 3).reshape(R, Hkv, M * P)
+
+
+def _cache_tokens(k_cache, block_table) -> int:
+    """Tokens a row can hold: Tmax, or max_pages * page with a table."""
+    if block_table is None:
+        return k_cache.shape[1]
+    return block_table.shape[1] * k_cache.shape[1]
+
+
+def _scatter_pages(cache, scale, slot, slot_scale, block_table, r: int, t0: int, t1: int):
+    """Tokens t0 .. t1-1 of table row r, from the slot-layout copy back into
+    the pool (bytes, and scales when there are any)."""
+    t = torch.arange(t0, t1, device=cache.device)
+    P = cache.shape[1]
+    pg, off = block_table[r, t // P].long(), t % P
+    cache.view(torch.uint8)[pg, off] = slot.view(torch.uint8)[r, t0:t1]
+    if scale is not None:
+        scale[pg, :, off] = slot_scale[r, :, t0:t1].T
+
+
 def decode_attention_hip_supported(q: torch.Tensor, num_kv_heads: int,
-                                   cache_dtype: Optional[torch.dtype] = None) -> bool:
+                                   cache_dtype: Optional[torch.dtype] = None,
+                                   page_size: Optional[int] = None) -> bool:
     """True when ``decode_attention`` runs the fused gfx950 kernel for a
     query of this device/dtype/geometry (else it runs the reference).
     ``cache_dtype``: None or bf16 for the bf16 cache, ``float8_e4m3fn`` for
-    the fp8 one."""
+    the fp8 one.  ``page_size``: the page of a paged cache (one called with a
+    ``block_table``), None for the slot cache."""
     if not use_hip(q):
+        return False
+    if page_size not in (None, PAGE_TOKENS):
         return False
     if cache_dtype not in (None, torch.bfloat16, FP8_KV_DTYPE):
         return False
@@ -298,18 +352,32 @@ def _positions_tensor(positions, N: int, device) -> torch.Tensor:
 @torch.no_grad()
 def decode_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
                          rows=None, lengths=None, max_len=None,
-                         k_scale=None, v_scale=None) -> torch.Tensor:
+                         k_scale=None, v_scale=None, block_table=None) -> torch.Tensor:
     """Plain per-row fp32 composition: rotate (the apply_rope_positions
     formula), round to the cache dtype, write, softmax over keys 0..p.
     The CPU path and the oracle of the kernel; ``max_len`` is unused.
     With fp8 caches the rotated bf16 K row and the V row are quantised
     (``quantize_kv_rows_fp8``), byte and scale are written, and the new token
-    is attended as its dequantised self, like every cached one."""
+    is attended as its dequantised self, like every cached one.
+    With ``block_table`` the caches are a paged pool of any page size: the
+    table rows are gathered into a slot-layout copy, the composition runs on
+    it, and each row's new token is scattered back to its page."""
     from .rope import apply_rope_positions
 
     _check_fp8_args("decode_attention_ref", k_cache, v_cache, k_scale, v_scale)
 
     N, _, H, D = q.shape
+    if block_table is not None:
+        _check_block_table("decode_attention_ref", block_table, k_cache)
+        ks, kss = _gather_pages(k_cache, k_scale, block_table)
+        vs, vss = _gather_pages(v_cache, v_scale, block_table)
+        o = decode_attention_ref(q, k_new, v_new, ks, vs, cos, sin, positions, rows=rows,
+                                 lengths=lengths, k_scale=kss, v_scale=vss)
+        row_l = rows.tolist() if rows is not None else range(N)
+        for r, p in zip(row_l, _positions_tensor(positions, N, q.device).tolist()):
+            _scatter_pages(k_cache, k_scale, ks, kss, block_table, r, p, p + 1)
+            _scatter_pages(v_cache, v_scale, vs, vss, block_table, r, p, p + 1)
+        return o
     Hkv = k_new.shape[2]
     rep = H // Hkv
     pos = _positions_tensor(positions, N, q.device)
@@ -339,7 +407,7 @@ def _shares_storage(a: torch.Tensor, b: torch.Tensor) -> bool:
 def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
                      rows=None, lengths=None, max_len=None,
                      impl: Optional[str] = None,
-                     k_scale=None, v_scale=None) -> torch.Tensor:
+                     k_scale=None, v_scale=None, block_table=None) -> torch.Tensor:
     """Fused RoPE + cache write + GQA decode attention (one kernel launch plus
     a small combine) for bf16 / head_dim 128 / H/Hkv in {1,2,4,8,16} on the
     GPU; ``decode_attention_ref`` otherwise.  ``positions`` is a long tensor
@@ -355,20 +423,30 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
     ``k_scale`` / ``v_scale``, fp32 [slots,Hkv,Tmax]: one power-of-two scale
     per (slot, kv head, token), each row stored as the e4m3 of x / scale
     (``quantize_kv_rows_fp8``).  They have one MFMA kernel for all five group
-    sizes, so ``impl`` must stay None."""
+    sizes, so ``impl`` must stay None.
+    ``block_table`` (int32 [table_rows, max_pages]) makes the caches a paged
+    pool [num_pages, page, Hkv, 128] (scales [num_pages, Hkv, page]): token t
+    of table row ``rows[n]`` lives at ``cache[block_table[row, t // page],
+    t % page]`` and ``lengths`` is [table_rows].  The same kernels serve
+    page == 64, in every cache dtype and group size; ``max_len`` then defaults
+    to ``max_pages * page``."""
     if impl not in _DECODE_IMPLS:
         raise ValueError(f"decode_attention: impl must be None, 'valu' or 'mfma', got {impl!r}")
     fp8 = _check_fp8_args("decode_attention", k_cache, v_cache, k_scale, v_scale)
     if fp8 and impl is not None:
         raise ValueError("decode_attention: impl names a bf16-cache kernel; an fp8 cache "
                          "takes impl=None")
-    if not decode_attention_hip_supported(q, k_new.shape[2], FP8_KV_DTYPE if fp8 else None):
+    if block_table is not None:
+        _check_block_table("decode_attention", block_table, k_cache)
+    page = k_cache.shape[1] if block_table is not None else None
+    if not decode_attention_hip_supported(q, k_new.shape[2], FP8_KV_DTYPE if fp8 else None,
+                                          page):
         if impl is not None:
             raise ValueError(f"decode_attention: impl={impl!r} needs the gfx950 kernel, which "
                              "does not serve this device/dtype/geometry")
         return decode_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin,
                                     positions, rows=rows, lengths=lengths, max_len=max_len,
-                                    k_scale=k_scale, v_scale=v_scale)
+                                    k_scale=k_scale, v_scale=v_scale, block_table=block_table)
     ext = extension()
     pos_t, upos = (None, positions) if isinstance(positions, int) else (positions, 0)
     if pos_t is not None and lengths is not None and _shares_storage(pos_t, lengths):
@@ -378,15 +456,17 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
         pos_t = pos_t.contiguous()
     if rows is not None:
         rows = rows.contiguous()
+    if block_table is not None:
+        block_table = block_table.contiguous()
     if max_len is None:
-        max_len = min(k_cache.shape[1], cos.shape[0])
+        max_len = min(_cache_tokens(k_cache, block_table), cos.shape[0])
     if fp8:
         return ext.attention_decode_fp8(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
                                         k_cache, v_cache, k_scale, v_scale, cos, sin, pos_t,
-                                        rows, lengths, upos, int(max_len), 0)
+                                        rows, lengths, upos, int(max_len), 0, block_table)
     return ext.attention_decode(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
                                 k_cache, v_cache, cos, sin, pos_t, rows, lengths,
-                                upos, int(max_len), 0, _DECODE_IMPLS[impl])
+                                upos, int(max_len), 0, _DECODE_IMPLS[impl], block_table)
 
 
 # ---------------------------------------------------------------------------
@@ -403,11 +483,14 @@ def decode_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
 # ---------------------------------------------------------------------------
 
 def extend_attention_hip_supported(q: torch.Tensor, num_kv_heads: int,
-                                   cache_dtype: Optional[torch.dtype] = None) -> bool:
+                                   cache_dtype: Optional[torch.dtype] = None,
+                                   page_size: Optional[int] = None) -> bool:
     """True when ``extend_attention`` runs the gfx950 kernels for a query of
     this device/dtype/geometry (else it runs the reference).  ``cache_dtype``
-    as for ``decode_attention_hip_supported``."""
+    and ``page_size`` as for ``decode_attention_hip_supported``."""
     if not use_hip(q):
+        return False
+    if page_size not in (None, PAGE_TOKENS):
         return False
     if cache_dtype not in (None, torch.bfloat16, FP8_KV_DTYPE):
         return False
@@ -423,11 +506,12 @@ def extend_attention_hip_supported(q: torch.Tensor, num_kv_heads: int,
 @torch.no_grad()
 def extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
                          q_lens=None, rows=None, lengths=None, max_len=None,
-                         k_scale=None, v_scale=None) -> torch.Tensor:
+                         k_scale=None, v_scale=None, block_table=None) -> torch.Tensor:
     """Plain per-row fp32 composition: rotate token i at p + i (the
     apply_rope_positions formula), round to the cache dtype, write, softmax
     over keys 0 .. p + i.  The CPU path and the oracle of the kernel;
-    ``max_len`` is unused.  fp8 caches as in ``decode_attention_ref``."""
+    ``max_len`` is unused.  fp8 caches and ``block_table`` as in
+    ``decode_attention_ref``."""
     from .rope import apply_rope_positions
 
     _check_fp8_args("extend_attention_ref", k_cache, v_cache, k_scale, v_scale)
@@ -437,6 +521,16 @@ def extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions,
     pos = _positions_tensor(positions, N, q.device).tolist()
     lens = q_lens.tolist() if q_lens is not None else [Sq] * N
     row_l = rows.tolist() if rows is not None else list(range(N))
+    if block_table is not None:
+        _check_block_table("extend_attention_ref", block_table, k_cache)
+        ks, kss = _gather_pages(k_cache, k_scale, block_table)
+        vs, vss = _gather_pages(v_cache, v_scale, block_table)
+        o = extend_attention_ref(q, k_new, v_new, ks, vs, cos, sin, positions, q_lens=q_lens,
+                                 rows=rows, lengths=lengths, k_scale=kss, v_scale=vss)
+        for r, p, ln in zip(row_l, pos, lens):
+            _scatter_pages(k_cache, k_scale, ks, kss, block_table, r, p, p + ln)
+            _scatter_pages(v_cache, v_scale, vs, vss, block_table, r, p, p + ln)
+        return o
     scale = 1.0 / (D ** 0.5)
     o = torch.zeros_like(q)
     for n, (r, p, ln) in enumerate(zip(row_l, pos, lens)):
@@ -461,7 +555,7 @@ def extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions,
 def extend_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
                      q_lens=None, rows=None, lengths=None, max_len=None,
                      chunk: int = 0, split: Optional[bool] = None,
-                     k_scale=None, v_scale=None) -> torch.Tensor:
+                     k_scale=None, v_scale=None, block_table=None) -> torch.Tensor:
     """Fused RoPE + cache write + GQA attention of Sq new tokens per row over
     the slot cache (an append launch, an MFMA attention launch and, on the
     split path, a combine) for bf16 / head_dim 128 / H/Hkv in {1,2,4,8} on the
@@ -472,12 +566,19 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
     fixed set, and the split (True) or direct (False) path instead of the
     choice by ``Sq * H/Hkv``.  ``float8_e4m3fn`` caches with ``k_scale`` /
     ``v_scale`` as for ``decode_attention``: the append quantises, the
-    attention kernel dequantises on its way into LDS."""
+    attention kernel dequantises on its way into LDS.  ``block_table`` as for
+    ``decode_attention``: a 64-token page is one key tile of the kernel, and a
+    chunk that crosses a page boundary is appended to both pages."""
     fp8 = _check_fp8_args("extend_attention", k_cache, v_cache, k_scale, v_scale)
-    if not extend_attention_hip_supported(q, k_new.shape[2], FP8_KV_DTYPE if fp8 else None):
+    if block_table is not None:
+        _check_block_table("extend_attention", block_table, k_cache)
+    page = k_cache.shape[1] if block_table is not None else None
+    if not extend_attention_hip_supported(q, k_new.shape[2], FP8_KV_DTYPE if fp8 else None,
+                                          page):
         return extend_attention_ref(q, k_new, v_new, k_cache, v_cache, cos, sin, positions,
                                     q_lens=q_lens, rows=rows, lengths=lengths,
-                                    max_len=max_len, k_scale=k_scale, v_scale=v_scale)
+                                    max_len=max_len, k_scale=k_scale, v_scale=v_scale,
+                                    block_table=block_table)
     ext = extension()
     pos_t, upos = (None, positions) if isinstance(positions, int) else (positions, 0)
     if lengths is not None:
@@ -486,14 +587,16 @@ def extend_attention(q, k_new, v_new, k_cache, v_cache, cos, sin, positions, *,
                                else t for t in (pos_t, q_lens, rows))
     pos_t, q_lens, rows = (t.contiguous() if t is not None else None
                            for t in (pos_t, q_lens, rows))
+    if block_table is not None:
+        block_table = block_table.contiguous()
     if max_len is None:
-        max_len = min(k_cache.shape[1], cos.shape[0])
+        max_len = min(_cache_tokens(k_cache, block_table), cos.shape[0])
     if fp8:
         return ext.attention_extend_fp8(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
                                         k_cache, v_cache, k_scale, v_scale, cos, sin, pos_t,
                                         q_lens, rows, lengths, upos, int(max_len), int(chunk),
-                                        -1 if split is None else int(bool(split)))
+                                        -1 if split is None else int(bool(split)), block_table)
     return ext.attention_extend(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
                                 k_cache, v_cache, cos, sin, pos_t, q_lens, rows, lengths,
                                 upos, int(max_len), int(chunk),
-                                -1 if split is None else int(bool(split)))
+                                -1 if split is None else int(bool(split)), block_table)

@@ -47,10 +47,11 @@ def build(verbose: bool = True, force: bool = False) -> Path:
     hipcc = str(rocm / "bin" / "hipcc")
 
     include_dirs = ce.include_paths() + [str(CSRC)]
-    objs = []
     build_dir = OUT_DIR / "_build"
     build_dir.mkdir(exist_ok=True)
-    for src in sources:
+    import sysconfig
+
+    def compile_one(src):
         obj = build_dir / (src.stem + ".o")
         cmd = [
             hipcc,
@@ -70,18 +71,23 @@ def build(verbose: bool = True, force: bool = False) -> Path:
         ]
         for inc in include_dirs:
             cmd += ["-I", inc]
-        # python headers
-        import sysconfig
-
-        cmd += ["-I", sysconfig.get_paths()["include"]]
-        if verbose:
-            print("[lpp build]", " ".join(cmd), flush=True)
+        cmd += ["-I", sysconfig.get_paths()["include"]]  # python headers
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src.name}:\n{r.stdout}\n{r.stderr}")
-        if r.stderr and verbose:
-            sys.stderr.write(r.stderr)
-        objs.append(obj)
+        if verbose:
+            # one write per translation unit, so the threads' lines do not interleave
+            sys.stdout.write("[lpp build] " + " ".join(cmd) + "\n" + r.stderr)
+            sys.stdout.flush()
+        return obj
+
+    # the translation units are independent (most of each one's time is the
+    # torch headers): compile them side by side, MAX_JOBS or up to 16 at once
+    from concurrent.futures import ThreadPoolExecutor
+
+    jobs = int(os.environ.get("MAX_JOBS") or min(os.cpu_count() or 1, 16))
+    with ThreadPoolExecutor(max_workers=max(1, min(jobs, len(sources)))) as pool:
+        objs = list(pool.map(compile_one, sources))
 
     link = [
         hipcc,

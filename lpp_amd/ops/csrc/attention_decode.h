@@ -5,6 +5,7 @@
 #pragma once
 
 #include "attention.h"
+#include "attn_paged.h"
 #include "common.h"
 
 namespace lpp {
@@ -23,6 +24,14 @@ constexpr bool kDecodeMfmaDefault8 = true;
 __device__ __forceinline__ uint32_t bf16_bits(float x) {
   return (uint32_t)__builtin_bit_cast(unsigned short, __float2bfloat16(x));
 }
+
+// What a launch needs of an optional block table (decode_check_args): the
+// device view (table null: slot layout) and how many rows `rows` may name -
+// the table's rows, or the cache's slots.
+struct DecodeTable {
+  PageTable pt;
+  int rows;
+};
 
 // Row metadata shared by both kernels.  A row whose cache row or position is
 // out of range is skipped (nothing read, nothing written, o = 0).
@@ -121,16 +130,18 @@ void launch_decode_mfma(int rep, int chunk, const at::Tensor& q, const at::Tenso
                         const at::Tensor& v_new, at::Tensor& k_cache, at::Tensor& v_cache,
                         const at::Tensor& cos_t, const at::Tensor& sin_t,
                         const int64_t* positions, const int64_t* rows, int64_t* lengths,
-                        at::Tensor& o, int uniform_pos, int max_len);
+                        at::Tensor& o, const DecodeTable& bt, int uniform_pos, int max_len);
 
 // The argument checks of attention_decode and attention_decode_fp8
-// (attention_decode.hip); with the scales given the caches must be e4m3.
-void decode_check_args(const char* who, const at::Tensor& q, const at::Tensor& k_new,
+// (attention_decode.hip); with the scales given the caches must be e4m3, with
+// block_table they are a paged pool.
+DecodeTable decode_check_args(const char* who, const at::Tensor& q, const at::Tensor& k_new,
                        const at::Tensor& v_new, const at::Tensor& k_cache,
                        const at::Tensor& v_cache, const at::Tensor& cos_t,
                        const at::Tensor& sin_t, const c10::optional<at::Tensor>& positions,
                        const c10::optional<at::Tensor>& rows,
                        const c10::optional<at::Tensor>& lengths, int64_t uniform_pos,
-                       int64_t max_len, const at::Tensor* k_scale, const at::Tensor* v_scale);
+                       int64_t max_len, const at::Tensor* k_scale, const at::Tensor* v_scale,
+                       const c10::optional<at::Tensor>& block_table);
 
 }  // namespace lpp

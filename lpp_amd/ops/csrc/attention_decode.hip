@@ -29,6 +29,17 @@
 //
 // Groups of 8 and 16 heads have an MFMA kernel of their own
 // (attention_decode_mfma.hip); attention_decode.h holds what the two share.
+//
+// PAGED (attn_paged.h): the caches are a pool of 64-key pages under a block
+// table.  A wave's C/4 keys lie in one page, or two at C = 512; it looks the
+// pages up once before the key loop (scalar loads, their latency under the
+// RoPE prologue) and a step of 16 or 8 keys adds the page's base instead of
+// the row's.  Lanes, steps, masks and merge orders are the slot path's, so a
+// row's bits are too.
+// gfx950 (hipcc -O3), C = 256, slot / paged: NumVgprs 134 / 134 (REP 1), 152 /
+// 152 (2), 198 / 198 (4), 204 / 204 (8); SGPRs 46-48 / 52; ScratchSize 0 and
+// the same waves/SIMD (3, 3, 2, 2) in both.  C = 128 and 512 likewise: at most
+// 2 VGPRs apart, scratch 0, occupancy equal.
 #include "attention_decode.h"
 
 namespace lpp {
@@ -61,12 +72,12 @@ __device__ __forceinline__ float row16_sum(float x) {
   return dpp_add<0x140>(x);  // row_mirror
 }
 
-template <int REP, int C>
+template <int REP, int C, bool PAGED>
 __global__ __launch_bounds__(kDecodeThreads, 2) void attn_decode_kernel(
     const __hip_bfloat16* __restrict__ q,      // [N,1,H,128]
     const __hip_bfloat16* __restrict__ k_new,  // [N,1,Hkv,128]
     const __hip_bfloat16* __restrict__ v_new,  // [N,1,Hkv,128]
-    __hip_bfloat16* k_cache,                   // [slots,Tmax,Hkv,128]
+    __hip_bfloat16* k_cache,                   // [slots,Tmax,Hkv,128]; PAGED: the pool
     __hip_bfloat16* v_cache,
     const float* __restrict__ cos_t,           // [Smax,64]
     const float* __restrict__ sin_t,
@@ -74,6 +85,7 @@ __global__ __launch_bounds__(kDecodeThreads, 2) void attn_decode_kernel(
     const int64_t* __restrict__ rows,          // [N] or null
     int64_t* lengths,                          // [slots] or null
     float* __restrict__ ws,                    // [N,H,J,kDecodeWs]
+    PageTable pt,                              // PAGED: slots counts the table's rows
     int uniform_pos, int max_len, int slots, int Tmax, int Hkv, int J, float c) {
   constexpr int KPW = C / kDecodeWaves;        // keys per wave
   // keys per wave step: G loads x 4 key rows; 8 heads leave registers for 2
@@ -101,6 +113,9 @@ __global__ __launch_bounds__(kDecodeThreads, 2) void attn_decode_kernel(
   const int lane = tid & (kWave - 1), wid = tid / kWave;
   const int lg = lane >> 4;                    // key within a 4-key load
   const int dl = lane & 15;                    // dim octet: dims dl*8 .. dl*8+7
+  const int wave0 = chunk0 + wid * KPW;        // first key of this wave
+  // where this wave's keys live: the row (hoisted by the compiler), or its pages
+  const DecodeRuns<PAGED, KPW> runs(pt, row.r, Tmax, Hkv, kvh, wave0, p);
 
   // ---- RoPE (pairs (d, d+64), fp32, rounded to bf16) -> LDS -----------------
   const float* cr = cos_t + (int64_t)p * HALF;
@@ -200,20 +215,20 @@ __global__ __launch_bounds__(kDecodeThreads, 2) void attn_decode_kernel(
   // Positions >= p of the row are never addressed: a load past the last cached
   // key is aimed at key p - 1 instead and its score masked, so the loop has no
   // branch and reads nothing stale and nothing written in this launch.
-  const int64_t row_base = ((row.r * Tmax) * (int64_t)Hkv + kvh) * ATTN_D;  // key 0
+  // (with pages, key p - 1 of a step that holds a cached key is in the step's page)
   const int64_t key_stride = (int64_t)Hkv * ATTN_D;
-  const int wave0 = chunk0 + wid * KPW;        // first key of this wave
   int nst = (p - wave0 + STEP - 1) / STEP;     // steps holding a cached key: a prefix
   nst = p <= wave0 ? 0 : (nst > NSTEP ? NSTEP : nst);
-  const __hip_bfloat16* kp = k_cache + row_base + dl * 8;
-  const __hip_bfloat16* vp = v_cache + row_base + dl * 8;
+  const __hip_bfloat16* kp = k_cache + dl * 8;
+  const __hip_bfloat16* vp = v_cache + dl * 8;
 
   uint4 kb[2][G], vb[2][G];
   auto load_step = [&](int s, uint4(&kd)[G], uint4(&vd)[G]) {
+    const int64_t base = runs.at(s * STEP).kv;  // key 0 of the row, or of the step's page
 #pragma unroll
     for (int i = 0; i < G; ++i) {
       const int key = wave0 + s * STEP + i * 4 + lg;
-      const int64_t off = (int64_t)(key < p ? key : p - 1) * key_stride;
+      const int64_t off = base + (int64_t)(key < p ? key : p - 1) * key_stride;
       kd[i] = *reinterpret_cast<const uint4*>(kp + off);
       vd[i] = *reinterpret_cast<const uint4*>(vp + off);
     }
@@ -253,10 +268,15 @@ __global__ __launch_bounds__(kDecodeThreads, 2) void attn_decode_kernel(
 
   // ---- cache write: the owner is the one workgroup per (n, kv head) ----------
   if (owner) {
-    const int64_t dst = row_base + (int64_t)p * key_stride;
-    if (tid < ATTN_D / 8) reinterpret_cast<uint4*>(k_cache + dst)[tid] = kn_s[tid];
-    else if (tid < ATTN_D / 4)
+    const KvRun at_p = kv_run<PAGED>(pt, row.r, Tmax, Hkv, kvh, p);
+    const int64_t dst = at_p.kv + (int64_t)p * key_stride;
+    if (!at_p.ok) {
+      // a table entry outside the pool: the token is not stored
+    } else if (tid < ATTN_D / 8) {
+      reinterpret_cast<uint4*>(k_cache + dst)[tid] = kn_s[tid];
+    } else if (tid < ATTN_D / 4) {
       reinterpret_cast<uint4*>(v_cache + dst)[tid - ATTN_D / 8] = vn_s[tid - ATTN_D / 8];
+    }
     if (lengths && kvh == 0 && tid == kWave) lengths[row.r] = (int64_t)p + 1;
   }
 
@@ -308,25 +328,25 @@ __global__ __launch_bounds__(kDecodeThreads, 2) void attn_decode_kernel(
   }
 }
 
-template <int REP, int C>
+template <int REP, int C, bool PAGED>
 static void launch_decode(const at::Tensor& q, const at::Tensor& k_new, const at::Tensor& v_new,
                           at::Tensor& k_cache, at::Tensor& v_cache, const at::Tensor& cos_t,
                           const at::Tensor& sin_t, const int64_t* positions,
                           const int64_t* rows, int64_t* lengths, at::Tensor& o,
-                          int uniform_pos, int max_len) {
+                          const DecodeTable& bt, int uniform_pos, int max_len) {
   const int N = q.size(0), H = q.size(2), Hkv = k_new.size(2);
-  const int slots = k_cache.size(0), Tmax = k_cache.size(1);
+  const int slots = bt.rows, Tmax = k_cache.size(1);
   const int J = (max_len + C - 1) / C;
   auto ws = at::empty({N, H, J, kDecodeWs}, q.options().dtype(at::kFloat));
   auto stream = current_stream();
-  hipLaunchKernelGGL((attn_decode_kernel<REP, C>), dim3(J, Hkv, N), dim3(kDecodeThreads), 0,
+  hipLaunchKernelGGL((attn_decode_kernel<REP, C, PAGED>), dim3(J, Hkv, N), dim3(kDecodeThreads), 0,
                      stream, (const __hip_bfloat16*)q.data_ptr(),
                      (const __hip_bfloat16*)k_new.data_ptr(),
                      (const __hip_bfloat16*)v_new.data_ptr(),
                      (__hip_bfloat16*)k_cache.data_ptr(), (__hip_bfloat16*)v_cache.data_ptr(),
                      cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), positions, rows,
-                     lengths, ws.data_ptr<float>(), uniform_pos, max_len, slots, Tmax, Hkv, J,
-                     attn_scale().c);
+                     lengths, ws.data_ptr<float>(), bt.pt, uniform_pos, max_len, slots, Tmax, Hkv,
+                     J, attn_scale().c);
   LPP_CHECK_HIP(hipGetLastError());
   launch_decode_combine<C>(ws, positions, rows, o, uniform_pos, max_len, slots, N, H, J);
 }
@@ -337,11 +357,15 @@ static void launch_decode_rep(int rep, const at::Tensor& q, const at::Tensor& k_
                               at::Tensor& v_cache, const at::Tensor& cos_t,
                               const at::Tensor& sin_t, const int64_t* positions,
                               const int64_t* rows, int64_t* lengths, at::Tensor& o,
-                              int uniform_pos, int max_len) {
-#define LPP_DECODE_REP(R)                                                                  \
-  case R:                                                                                  \
-    return launch_decode<R, C>(q, k_new, v_new, k_cache, v_cache, cos_t, sin_t, positions, \
-                               rows, lengths, o, uniform_pos, max_len)
+                              const DecodeTable& bt, int uniform_pos, int max_len) {
+#define LPP_DECODE_REP(R)                                                                   \
+  case R:                                                                                   \
+    if (bt.pt.table)                                                                        \
+      return launch_decode<R, C, true>(q, k_new, v_new, k_cache, v_cache, cos_t, sin_t,     \
+                                       positions, rows, lengths, o, bt, uniform_pos,        \
+                                       max_len);                                            \
+    return launch_decode<R, C, false>(q, k_new, v_new, k_cache, v_cache, cos_t, sin_t,      \
+                                      positions, rows, lengths, o, bt, uniform_pos, max_len)
   switch (rep) {
     LPP_DECODE_REP(1);
     LPP_DECODE_REP(2);
@@ -362,13 +386,17 @@ static bool disjoint(const void* a, size_t na, const void* b, size_t nb) {
 
 // The argument checks of attention_decode and attention_decode_fp8.  The
 // caches are bf16, or e4m3 when the two scales ([slots,Hkv,Tmax] fp32) are given.
-void decode_check_args(const char* who, const at::Tensor& q, const at::Tensor& k_new,
+// With block_table (int32 [table_rows, max_pages]) the caches are a pool of
+// 64-key pages and rows / lengths / N count table rows.  Returns what the
+// launch needs of the table.
+DecodeTable decode_check_args(const char* who, const at::Tensor& q, const at::Tensor& k_new,
                        const at::Tensor& v_new, const at::Tensor& k_cache,
                        const at::Tensor& v_cache, const at::Tensor& cos_t,
                        const at::Tensor& sin_t, const c10::optional<at::Tensor>& positions,
                        const c10::optional<at::Tensor>& rows,
                        const c10::optional<at::Tensor>& lengths, int64_t uniform_pos,
-                       int64_t max_len, const at::Tensor* k_scale, const at::Tensor* v_scale) {
+                       int64_t max_len, const at::Tensor* k_scale, const at::Tensor* v_scale,
+                       const c10::optional<at::Tensor>& block_table) {
   const at::ScalarType cache_t = k_scale ? at::kFloat8_e4m3fn : at::kBFloat16;
 
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, who, ": bf16 CUDA q required");
@@ -394,9 +422,27 @@ void decode_check_args(const char* who, const at::Tensor& q, const at::Tensor& k
                     t->dim() == 2 && t->size(1) == ATTN_D / 2 && t->device() == q.device(),
                 who, ": cos/sin must be contiguous fp32 [Smax,64]");
   TORCH_CHECK(cos_t.size(0) == sin_t.size(0), who, ": cos/sin length mismatch");
-  const int64_t slots = k_cache.size(0), Tmax = k_cache.size(1);
-  TORCH_CHECK(max_len >= 1 && max_len <= Tmax && max_len <= cos_t.size(0), who,
-              ": max_len ", max_len, " must be in [1, min(Tmax, rope table)]");
+  const int64_t Tmax = k_cache.size(1);
+  int64_t slots = k_cache.size(0), row_tokens = Tmax;  // rows of the cache, tokens of a row
+  DecodeTable bt{{nullptr, 0, 0}, (int)slots};
+  if (block_table.has_value()) {
+    const at::Tensor& t = *block_table;
+    TORCH_CHECK(Tmax == kPageTokens, who, ": a paged cache is [num_pages,", kPageTokens,
+                ",Hkv,128], got ", Tmax, " tokens per page");
+    TORCH_CHECK(t.is_cuda() && t.device() == q.device() && t.scalar_type() == at::kInt &&
+                    t.is_contiguous() && t.dim() == 2 && t.size(0) >= 1 && t.size(1) >= 1,
+                who, ": block_table must be a contiguous int32 [table_rows,max_pages] on q's "
+                     "device");
+    TORCH_CHECK(slots >= 1 && slots < ((int64_t)1 << 31) / kPageTokens &&
+                    t.size(0) < ((int64_t)1 << 31) && t.size(1) < ((int64_t)1 << 31) / kPageTokens,
+                who, ": pool or block_table out of range");
+    bt = DecodeTable{{t.data_ptr<int>(), (int)t.size(1), (int)slots}, (int)t.size(0)};
+    slots = t.size(0);
+    row_tokens = t.size(1) * kPageTokens;
+  }
+  TORCH_CHECK(max_len >= 1 && max_len <= row_tokens && max_len <= cos_t.size(0), who,
+              ": max_len ", max_len, " must be in [1, min(",
+              block_table.has_value() ? "max_pages * 64" : "Tmax", ", rope table)]");
   TORCH_CHECK(k_cache.numel() < ((int64_t)1 << 40) && N <= 65535 && H <= 65535, who,
               ": shape out of range");  // grid y/z limits; 64-bit offsets beyond
 
@@ -426,21 +472,31 @@ void decode_check_args(const char* who, const at::Tensor& q, const at::Tensor& k
   TORCH_CHECK(lpp::disjoint(k_cache.data_ptr(), k_cache.nbytes(), v_cache.data_ptr(),
                             v_cache.nbytes()),
               who, ": k_cache and v_cache must not alias");
-  if (!k_scale) return;
+  if (block_table.has_value()) {
+    // read by every workgroup while the owners write the caches and lengths
+    std::vector<const at::Tensor*> written = {&k_cache, &v_cache};
+    if (lengths.has_value()) written.push_back(&lengths.value());
+    for (const at::Tensor* u : written)
+      TORCH_CHECK(lpp::disjoint(block_table->data_ptr(), block_table->nbytes(), u->data_ptr(),
+                                u->nbytes()),
+                  who, ": block_table must not alias lengths or the caches");
+  }
+  if (!k_scale) return bt;
   for (const at::Tensor* t : {k_scale, v_scale}) {
     TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kFloat &&
-                    t->is_contiguous() && t->dim() == 3 && t->size(0) == slots &&
+                    t->is_contiguous() && t->dim() == 3 && t->size(0) == k_cache.size(0) &&
                     t->size(1) == Hkv && t->size(2) == Tmax,
                 who, ": k_scale/v_scale must be contiguous fp32 [slots,Hkv,Tmax] on q's device");
     // written by one workgroup while others read every other argument
     std::vector<const at::Tensor*> others = {&q, &k_new, &v_new, &k_cache, &v_cache, &cos_t, &sin_t};
-    for (const c10::optional<at::Tensor>* o : {&positions, &rows, &lengths})
+    for (const c10::optional<at::Tensor>* o : {&positions, &rows, &lengths, &block_table})
       if (o->has_value()) others.push_back(&o->value());
     if (t == v_scale) others.push_back(k_scale);
     for (const at::Tensor* u : others)
       TORCH_CHECK(lpp::disjoint(t->data_ptr(), t->nbytes(), u->data_ptr(), u->nbytes()), who,
                   ": k_scale/v_scale must not alias another argument");
   }
+  return bt;
 }
 
 }  // namespace lpp
@@ -455,16 +511,19 @@ int64_t attention_decode_chunk() { return lpp::kDecodeChunk; }
 // impl = 0: the kernel by group size (kDecodeMfmaDefault8), 1: the vector-ALU
 // kernel (H/Hkv <= 8), 2: the MFMA kernel (H/Hkv 8 or 16).  The choice never
 // depends on N or max_len: the two kernels differ in the last bits.
+// block_table: the paged layout (attn_paged.h), the same kernels and choices.
 at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
                             at::Tensor sin_t, c10::optional<at::Tensor> positions,
                             c10::optional<at::Tensor> rows,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                            int64_t max_len, int64_t chunk, int64_t impl) {
+                            int64_t max_len, int64_t chunk, int64_t impl,
+                            c10::optional<at::Tensor> block_table) {
   const char* who = "attention_decode";
   TORCH_CHECK(impl >= 0 && impl <= 2, who, ": impl must be 0 (by geometry), 1 (valu) or 2 (mfma)");
-  lpp::decode_check_args(who, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t, positions, rows,
-                         lengths, uniform_pos, max_len, nullptr, nullptr);
+  const lpp::DecodeTable bt =
+      lpp::decode_check_args(who, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t, positions,
+                             rows, lengths, uniform_pos, max_len, nullptr, nullptr, block_table);
   const int64_t N = q.size(0), H = q.size(2), Hkv = k_new.size(2);
 
   auto o = at::empty_like(q);
@@ -481,13 +540,13 @@ at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
   TORCH_CHECK(impl != 1 || rep != 16, who, ": H/Hkv 16 has the MFMA kernel only");
   if (impl == 2 || (impl == 0 && (rep == 16 || (rep == 8 && lpp::kDecodeMfmaDefault8)))) {
     lpp::launch_decode_mfma(rep, (int)chunk, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t,
-                            pp, rp, lp, o, (int)uniform_pos, (int)max_len);
+                            pp, rp, lp, o, bt, (int)uniform_pos, (int)max_len);
     return o;
   }
 #define LPP_DECODE_CHUNK(CC)                                                            \
   case CC:                                                                               \
     lpp::launch_decode_rep<CC>(rep, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t, pp, \
-                               rp, lp, o, (int)uniform_pos, (int)max_len);               \
+                               rp, lp, o, bt, (int)uniform_pos, (int)max_len);           \
     break
   switch (chunk) {
     LPP_DECODE_CHUNK(128);

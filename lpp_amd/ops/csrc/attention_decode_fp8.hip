@@ -39,17 +39,28 @@
 // bf16 row, so it is attended as exactly what a later call reads back.
 //
 // Every merge order is fixed, so a row's bits depend on its own data and p alone.
+//
+// PAGED (attn_paged.h): as in attention_decode_mfma.hip - the one or two page
+// ids of a wave's keys come from scalar loads ahead of the prologue and a step
+// adds its page's base.  The scales take the same lookup, scale[page, hkv,
+// t & 63]: a step's 32 scales stay one dense run.  The new token's bytes and
+// scale go to the page of key p.
+// The slot instantiation keeps the row's base folded into its per-lane
+// pointers, as it always had; the paged one adds the page's base per step.
+// gfx950 (hipcc -O3), slot / paged, every REP: NumVgprs 105-106 / 103-104
+// (C = 128, 4 waves/SIMD), 144 / 148 (C = 256, 3), 144 / 140 (C = 512, 3);
+// ScratchSize 0 everywhere.
 #include "attention_decode.h"
 #include "attn_fp8.h"
 
 namespace lpp {
 
-template <int REP, int C>
+template <int REP, int C, bool PAGED>
 __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
     const __hip_bfloat16* __restrict__ q,      // [N,1,H,128]
     const __hip_bfloat16* __restrict__ k_new,  // [N,1,Hkv,128]
     const __hip_bfloat16* __restrict__ v_new,  // [N,1,Hkv,128]
-    uint8_t* k_cache,                          // [slots,Tmax,Hkv,128] e4m3
+    uint8_t* k_cache,                          // [slots,Tmax,Hkv,128] e4m3; PAGED: the pool
     uint8_t* v_cache,
     float* k_scale,                            // [slots,Hkv,Tmax]
     float* v_scale,
@@ -59,6 +70,7 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
     const int64_t* __restrict__ rows,          // [N] or null
     int64_t* lengths,                          // [slots] or null
     float* __restrict__ ws,                    // [N,H,J,kDecodeWs]
+    PageTable pt,                              // PAGED: slots counts the table's rows
     int uniform_pos, int max_len, int slots, int Tmax, int Hkv, int J, float c) {
   static_assert(REP >= 1 && REP <= 16, "the group's heads are one MFMA tile of 16 columns");
   constexpr int KPW = C / kDecodeWaves;        // keys per wave
@@ -90,9 +102,21 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
   const int g = lane >> 4;                     // lane group
   const int c8 = lane & 7, kr = lane >> 3;     // V: 16-dim run and key of a load
 
-  const int64_t row_base = ((row.r * Tmax) * (int64_t)Hkv + kvh) * ATTN_D;  // key 0, bytes
+  // key 0 of the row in the slot layout; PAGED: a step adds its page's (page_kv)
+  const int64_t row_base = PAGED ? 0 : ((row.r * Tmax) * (int64_t)Hkv + kvh) * ATTN_D;  // bytes
   const int64_t key_stride = (int64_t)Hkv * ATTN_D;
-  const int64_t scale_base = (row.r * Hkv + kvh) * (int64_t)Tmax;          // key 0
+  const int64_t scale_base = PAGED ? 0 : (row.r * Hkv + kvh) * (int64_t)Tmax;
+  const int wave0 = chunk0 + wid * KPW;        // first key of this wave
+  // PAGED: where this wave's keys and scales live, its one or two pages
+  [[maybe_unused]] const DecodeRuns<PAGED, KPW> runs(pt, row.r, Tmax, Hkv, kvh, wave0, p);
+  auto page_kv = [&](int key0) -> int64_t {
+    if constexpr (PAGED) return runs.at(key0 - wave0).kv;
+    else return 0;
+  };
+  auto page_scale = [&](int key0) -> int64_t {
+    if constexpr (PAGED) return runs.at(key0 - wave0).scale;
+    else return 0;
+  };
 
   // ---- RoPE (pairs (d, d+64), fp32, rounded to bf16) -> LDS -----------------
   const float* cr = cos_t + (int64_t)p * HALF;
@@ -129,6 +153,8 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
   // Wave 0 takes K, wave 1 V; lane l holds dims 2l and 2l+1.  The cache entry
   // at p is read by nobody in this launch, so it is stored right here.
   if (owner) {                                 // workgroup-uniform
+    KvRun at_p{0, 0, true};                    // PAGED: the page of key p
+    if constexpr (PAGED) at_p = kv_run<PAGED>(pt, row.r, Tmax, Hkv, kvh, p);
     if (wid < 2) {
       uint32_t* rw = reinterpret_cast<uint32_t*>(wid == 0 ? kn_s : vn_s);
       const uint32_t w = rw[lane];
@@ -141,9 +167,12 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
       const uint32_t qb = fp8_pack2(__fmul_rn(a, inv), __fmul_rn(b, inv));
       const fp8_f32x2 dq = fp8_unpack2(qb);
       rw[lane] = cvt_pk_bf16(__fmul_rn(dq[0], sc), __fmul_rn(dq[1], sc));  // exact
-      uint8_t* dst = (wid == 0 ? k_cache : v_cache) + row_base + (int64_t)p * key_stride;
-      reinterpret_cast<unsigned short*>(dst)[lane] = (unsigned short)qb;
-      if (lane == 0) (wid == 0 ? k_scale : v_scale)[scale_base + p] = sc;
+      // (a table entry outside the pool: the token is not stored)
+      uint8_t* dst =
+          (wid == 0 ? k_cache : v_cache) + row_base + at_p.kv + (int64_t)p * key_stride;
+      if (at_p.ok) reinterpret_cast<unsigned short*>(dst)[lane] = (unsigned short)qb;
+      if (at_p.ok && lane == 0)
+        (wid == 0 ? k_scale : v_scale)[scale_base + at_p.scale + p] = sc;
     } else if (lengths && kvh == 0 && tid == 2 * kWave) {
       lengths[row.r] = (int64_t)p + 1;
     }
@@ -164,8 +193,8 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
 #pragma unroll
   for (int dt = 0; dt < 8; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int wave0 = chunk0 + wid * KPW;        // first key of this wave
   // K of tile t: key +16t + l16, 32 bytes at g*32.  V load i: key +8i + kr, 16 bytes.
+  // All four from key 0 of the row; PAGED: of the step's page, added per step.
   const uint8_t* kp = k_cache + row_base + (int64_t)l16 * key_stride + g * 32;
   const uint8_t* vp = v_cache + row_base + (int64_t)kr * key_stride + c8 * 16;
   const float* ksp = k_scale + scale_base + l16;
@@ -184,19 +213,23 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
   bf16x8 kf[2][4];
 
   auto load_k = [&](int key0) {                // 32 cached keys from key0
+    const uint8_t* kq = kp + page_kv(key0);
+    const float* ksq = ksp + page_scale(key0);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      const uint4* src = reinterpret_cast<const uint4*>(kp + (key0 + 16 * t) * key_stride);
+      const uint4* src = reinterpret_cast<const uint4*>(kq + (key0 + 16 * t) * key_stride);
       kraw[t][0] = src[0];
       kraw[t][1] = src[1];
-      ksc[t] = ksp[key0 + 16 * t];
+      ksc[t] = ksq[key0 + 16 * t];
     }
   };
   auto load_v = [&](int key0) {
+    const uint8_t* vq = vp + page_kv(key0);
+    const float* vsq = vsp + page_scale(key0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      vraw[i] = *reinterpret_cast<const uint4*>(vp + (key0 + 8 * i) * key_stride);
-      vsc[i] = vsp[key0 + 8 * i];
+      vraw[i] = *reinterpret_cast<const uint4*>(vq + (key0 + 8 * i) * key_stride);
+      vsc[i] = vsq[key0 + 8 * i];
     }
   };
   auto convert_k = [&]() {
@@ -291,16 +324,20 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
   // has to be finite).
   if (nfull < NSTEP && p >= wave0 && p - wave0 < KPW) {
     const int key0 = wave0 + nfull * STEP;     // key0 <= p < key0 + 32
+    const uint8_t* kq = kp + page_kv(key0);
+    const uint8_t* vq = vp + page_kv(key0);
+    const float* ksq = ksp + page_scale(key0);
+    const float* vsq = vsp + page_scale(key0);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int key = key0 + 16 * t + l16;
       kraw[t][0] = kraw[t][1] = make_uint4(0u, 0u, 0u, 0u);
       ksc[t] = 1.f;
       if (key < p) {
-        const uint4* src = reinterpret_cast<const uint4*>(kp + (key0 + 16 * t) * key_stride);
+        const uint4* src = reinterpret_cast<const uint4*>(kq + (key0 + 16 * t) * key_stride);
         kraw[t][0] = src[0];
         kraw[t][1] = src[1];
-        ksc[t] = ksp[key0 + 16 * t];
+        ksc[t] = ksq[key0 + 16 * t];
       }
     }
     convert_k();
@@ -316,8 +353,8 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
       uint4 w = make_uint4(0u, 0u, 0u, 0u);
       float sc = 1.f;
       if (key < p) {
-        w = *reinterpret_cast<const uint4*>(vp + (key0 + 8 * i) * key_stride);
-        sc = vsp[key0 + 8 * i];
+        w = *reinterpret_cast<const uint4*>(vq + (key0 + 8 * i) * key_stride);
+        sc = vsq[key0 + 8 * i];
       }
       bf16x8 lo = fp8x8_to_bf16(w.x, w.y, sc), hi = fp8x8_to_bf16(w.z, w.w, sc);
       if (key == p) {
@@ -374,25 +411,25 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_fp8_kernel(
   }
 }
 
-template <int REP, int C>
+template <int REP, int C, bool PAGED>
 static void launch_decode_fp8(const at::Tensor& q, const at::Tensor& k_new,
                               const at::Tensor& v_new, at::Tensor& k_cache, at::Tensor& v_cache,
                               at::Tensor& k_scale, at::Tensor& v_scale, const at::Tensor& cos_t,
                               const at::Tensor& sin_t, const int64_t* positions,
                               const int64_t* rows, int64_t* lengths, at::Tensor& o,
-                              int uniform_pos, int max_len) {
+                              const DecodeTable& bt, int uniform_pos, int max_len) {
   const int N = q.size(0), H = q.size(2), Hkv = k_new.size(2);
-  const int slots = k_cache.size(0), Tmax = k_cache.size(1);
+  const int slots = bt.rows, Tmax = k_cache.size(1);
   const int J = (max_len + C - 1) / C;
   auto ws = at::empty({N, H, J, kDecodeWs}, q.options().dtype(at::kFloat));
-  hipLaunchKernelGGL((attn_decode_fp8_kernel<REP, C>), dim3(J, Hkv, N), dim3(kDecodeThreads), 0,
+  hipLaunchKernelGGL((attn_decode_fp8_kernel<REP, C, PAGED>), dim3(J, Hkv, N), dim3(kDecodeThreads), 0,
                      current_stream(), (const __hip_bfloat16*)q.data_ptr(),
                      (const __hip_bfloat16*)k_new.data_ptr(),
                      (const __hip_bfloat16*)v_new.data_ptr(), (uint8_t*)k_cache.data_ptr(),
                      (uint8_t*)v_cache.data_ptr(), k_scale.data_ptr<float>(),
                      v_scale.data_ptr<float>(), cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
-                     positions, rows, lengths, ws.data_ptr<float>(), uniform_pos, max_len, slots,
-                     Tmax, Hkv, J, attn_scale().c);
+                     positions, rows, lengths, ws.data_ptr<float>(), bt.pt, uniform_pos, max_len,
+                     slots, Tmax, Hkv, J, attn_scale().c);
   LPP_CHECK_HIP(hipGetLastError());
   launch_decode_combine<C>(ws, positions, rows, o, uniform_pos, max_len, slots, N, H, J);
 }
@@ -400,17 +437,20 @@ static void launch_decode_fp8(const at::Tensor& q, const at::Tensor& k_new,
 }  // namespace lpp
 
 // attention_decode over e4m3 caches with per-(slot, kv head, token) scales.
-// chunk as for attention_decode; there is one kernel, so no impl.
+// chunk as for attention_decode; there is one kernel, so no impl.  block_table:
+// the paged layout (attn_paged.h), scales [num_pages,Hkv,64].
 at::Tensor attention_decode_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                                 at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale,
                                 at::Tensor v_scale, at::Tensor cos_t, at::Tensor sin_t,
                                 c10::optional<at::Tensor> positions,
                                 c10::optional<at::Tensor> rows,
                                 c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                                int64_t max_len, int64_t chunk) {
+                                int64_t max_len, int64_t chunk,
+                                c10::optional<at::Tensor> block_table) {
   const char* who = "attention_decode_fp8";
-  lpp::decode_check_args(who, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t, positions, rows,
-                         lengths, uniform_pos, max_len, &k_scale, &v_scale);
+  const lpp::DecodeTable bt =
+      lpp::decode_check_args(who, q, k_new, v_new, k_cache, v_cache, cos_t, sin_t, positions,
+                             rows, lengths, uniform_pos, max_len, &k_scale, &v_scale, block_table);
   auto o = at::empty_like(q);
   if (q.size(0) == 0) return o;
   const int64_t* pp = positions.has_value() ? positions->data_ptr<int64_t>() : nullptr;
@@ -418,11 +458,17 @@ at::Tensor attention_decode_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new
   int64_t* lp = lengths.has_value() ? lengths->data_ptr<int64_t>() : nullptr;
   const int rep = (int)(q.size(2) / k_new.size(2));
   if (chunk == 0) chunk = lpp::kDecodeChunk;
-#define LPP_DECODE_FP8(R, CC)                                                                \
-  if (rep == R && chunk == CC) {                                                             \
-    lpp::launch_decode_fp8<R, CC>(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cos_t, \
-                                  sin_t, pp, rp, lp, o, (int)uniform_pos, (int)max_len);     \
-    return o;                                                                                \
+#define LPP_DECODE_FP8(R, CC)                                                                 \
+  if (rep == R && chunk == CC) {                                                              \
+    if (bt.pt.table)                                                                          \
+      lpp::launch_decode_fp8<R, CC, true>(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, \
+                                          cos_t, sin_t, pp, rp, lp, o, bt, (int)uniform_pos,  \
+                                          (int)max_len);                                      \
+    else                                                                                      \
+      lpp::launch_decode_fp8<R, CC, false>(q, k_new, v_new, k_cache, v_cache, k_scale,        \
+                                           v_scale, cos_t, sin_t, pp, rp, lp, o, bt,          \
+                                           (int)uniform_pos, (int)max_len);                   \
+    return o;                                                                                 \
   }
 #define LPP_DECODE_FP8_CHUNKS(R) LPP_DECODE_FP8(R, 128) LPP_DECODE_FP8(R, 256) LPP_DECODE_FP8(R, 512)
   LPP_DECODE_FP8_CHUNKS(1)

@@ -51,16 +51,26 @@
 //
 // Every merge order is fixed (lane groups, waves, chunks), so a row's bits
 // depend on its own data and p alone.
+//
+// PAGED (attn_paged.h): a step of 32 keys is half a 64-key page, so its page id
+// is wave-uniform.  A wave's C/4 keys are one page, or two at C = 512; both
+// ids are fetched by scalar loads before the RoPE prologue, and a step adds
+// its page's base (SGPRs) where the slot layout adds the row's.  The fragment
+// layouts, the staging, the predicated owner step and every merge order are
+// untouched, so paged and slot results are bit-identical.
+// gfx950 (hipcc -O3), slot / paged, REP 8 and 16 alike: NumVgprs 124 / 124
+// (C = 128, 4 waves/SIMD), 158 / 158 (C = 256, 3), 158 / 154 (C = 512, 3);
+// SGPRs 48-64 / 54-71; ScratchSize 0 everywhere.
 #include "attention_decode.h"
 
 namespace lpp {
 
-template <int REP, int C>
+template <int REP, int C, bool PAGED>
 __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
     const __hip_bfloat16* __restrict__ q,      // [N,1,H,128]
     const __hip_bfloat16* __restrict__ k_new,  // [N,1,Hkv,128]
     const __hip_bfloat16* __restrict__ v_new,  // [N,1,Hkv,128]
-    __hip_bfloat16* k_cache,                   // [slots,Tmax,Hkv,128]
+    __hip_bfloat16* k_cache,                   // [slots,Tmax,Hkv,128]; PAGED: the pool
     __hip_bfloat16* v_cache,
     const float* __restrict__ cos_t,           // [Smax,64]
     const float* __restrict__ sin_t,
@@ -68,6 +78,7 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
     const int64_t* __restrict__ rows,          // [N] or null
     int64_t* lengths,                          // [slots] or null
     float* __restrict__ ws,                    // [N,H,J,kDecodeWs]
+    PageTable pt,                              // PAGED: slots counts the table's rows
     int uniform_pos, int max_len, int slots, int Tmax, int Hkv, int J, float c) {
   static_assert(REP == 8 || REP == 16, "one MFMA tile of heads: 8 (half empty) or 16");
   constexpr int KPW = C / kDecodeWaves;        // keys per wave
@@ -97,6 +108,9 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
   const int wid = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int l16 = lane & 15;                   // K: key of a tile; Q, S, P, O: head
   const int g = lane >> 4;                     // lane group
+  const int wave0 = chunk0 + wid * KPW;        // first key of this wave
+  // where this wave's keys live: the row, or its one or two pages
+  const DecodeRuns<PAGED, KPW> runs(pt, row.r, Tmax, Hkv, kvh, wave0, p);
 
   // ---- RoPE (pairs (d, d+64), fp32, rounded to bf16) -> LDS -----------------
   const float* cr = cos_t + (int64_t)p * HALF;
@@ -143,12 +157,11 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
 #pragma unroll
   for (int dt = 0; dt < 8; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int64_t row_base = ((row.r * Tmax) * (int64_t)Hkv + kvh) * ATTN_D;  // key 0
   const int64_t key_stride = (int64_t)Hkv * ATTN_D;
-  const int wave0 = chunk0 + wid * KPW;        // first key of this wave
   // K fragment of (tile t, k-step ks): key +16t, dims +32ks.  V load i: key +4i.
-  const __hip_bfloat16* kp = k_cache + row_base + (int64_t)l16 * key_stride + g * 8;
-  const __hip_bfloat16* vp = v_cache + row_base + (int64_t)g * key_stride + l16 * 8;
+  // Both from key 0 of the row, or of the step's page (runs.at).
+  const __hip_bfloat16* kp = k_cache + (int64_t)l16 * key_stride + g * 8;
+  const __hip_bfloat16* vp = v_cache + (int64_t)g * key_stride + l16 * 8;
 
   char* vst = buf_s + wid * kVStageBytes;      // this wave's staging
   // load i stores chunk l16 of row 4i + g = 8(i>>1) + 4(i&1) + g
@@ -161,16 +174,18 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
   uint4 vr[8];
 
   auto load_k = [&](int key0) {                // 32 cached keys from key0
+    const __hip_bfloat16* kq = kp + runs.at(key0 - wave0).kv;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks)
-        kf[t][ks] = *reinterpret_cast<const bf16x8*>(kp + (key0 + 16 * t) * key_stride + 32 * ks);
+        kf[t][ks] = *reinterpret_cast<const bf16x8*>(kq + (key0 + 16 * t) * key_stride + 32 * ks);
   };
   auto load_v = [&](int key0) {
+    const __hip_bfloat16* vq = vp + runs.at(key0 - wave0).kv;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-      vr[i] = *reinterpret_cast<const uint4*>(vp + (key0 + 4 * i) * key_stride);
+      vr[i] = *reinterpret_cast<const uint4*>(vq + (key0 + 4 * i) * key_stride);
   };
   auto stage_v = [&]() {
 #pragma unroll
@@ -244,6 +259,7 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
   // LDS, zeros beyond (their P is 0; staged V has to be finite).
   if (nfull < NSTEP && p >= wave0 && p - wave0 < KPW) {
     const int key0 = wave0 + nfull * STEP;     // key0 <= p < key0 + 32
+    const int64_t base = runs.at(key0 - wave0).kv;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int key = key0 + 16 * t + l16;
@@ -251,7 +267,7 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
       for (int ks = 0; ks < 4; ++ks) {
         uint4 w = make_uint4(0u, 0u, 0u, 0u);
         if (key < p)
-          w = *reinterpret_cast<const uint4*>(kp + (key0 + 16 * t) * key_stride + 32 * ks);
+          w = *reinterpret_cast<const uint4*>(kp + base + (key0 + 16 * t) * key_stride + 32 * ks);
         else if (key == p)
           w = kn_s[ks * 4 + g];
         kf[t][ks] = __builtin_bit_cast(bf16x8, w);
@@ -262,7 +278,7 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
       const int key = key0 + 4 * i + g;
       uint4 w = make_uint4(0u, 0u, 0u, 0u);
       if (key < p)
-        w = *reinterpret_cast<const uint4*>(vp + (key0 + 4 * i) * key_stride);
+        w = *reinterpret_cast<const uint4*>(vp + base + (key0 + 4 * i) * key_stride);
       else if (key == p)
         w = vn_s[l16];
       vr[i] = w;
@@ -280,10 +296,15 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
 
   // ---- cache write: the owner is the one workgroup per (n, kv head) ----------
   if (owner) {
-    const int64_t dst = row_base + (int64_t)p * key_stride;
-    if (tid < ATTN_D / 8) reinterpret_cast<uint4*>(k_cache + dst)[tid] = kn_s[tid];
-    else if (tid < ATTN_D / 4)
+    const KvRun at_p = kv_run<PAGED>(pt, row.r, Tmax, Hkv, kvh, p);
+    const int64_t dst = at_p.kv + (int64_t)p * key_stride;
+    if (!at_p.ok) {
+      // a table entry outside the pool: the token is not stored
+    } else if (tid < ATTN_D / 8) {
+      reinterpret_cast<uint4*>(k_cache + dst)[tid] = kn_s[tid];
+    } else if (tid < ATTN_D / 4) {
       reinterpret_cast<uint4*>(v_cache + dst)[tid - ATTN_D / 8] = vn_s[tid - ATTN_D / 8];
+    }
     if (lengths && kvh == 0 && tid == kWave) lengths[row.r] = (int64_t)p + 1;
   }
 
@@ -324,25 +345,25 @@ __global__ __launch_bounds__(kDecodeThreads, 3) void attn_decode_mfma_kernel(
   }
 }
 
-template <int REP, int C>
+template <int REP, int C, bool PAGED>
 static void launch_decode_mfma_rc(const at::Tensor& q, const at::Tensor& k_new,
                                   const at::Tensor& v_new, at::Tensor& k_cache,
                                   at::Tensor& v_cache, const at::Tensor& cos_t,
                                   const at::Tensor& sin_t, const int64_t* positions,
                                   const int64_t* rows, int64_t* lengths, at::Tensor& o,
-                                  int uniform_pos, int max_len) {
+                                  const DecodeTable& bt, int uniform_pos, int max_len) {
   const int N = q.size(0), H = q.size(2), Hkv = k_new.size(2);
-  const int slots = k_cache.size(0), Tmax = k_cache.size(1);
+  const int slots = bt.rows, Tmax = k_cache.size(1);
   const int J = (max_len + C - 1) / C;
   auto ws = at::empty({N, H, J, kDecodeWs}, q.options().dtype(at::kFloat));
-  hipLaunchKernelGGL((attn_decode_mfma_kernel<REP, C>), dim3(J, Hkv, N), dim3(kDecodeThreads),
+  hipLaunchKernelGGL((attn_decode_mfma_kernel<REP, C, PAGED>), dim3(J, Hkv, N), dim3(kDecodeThreads),
                      0, current_stream(), (const __hip_bfloat16*)q.data_ptr(),
                      (const __hip_bfloat16*)k_new.data_ptr(),
                      (const __hip_bfloat16*)v_new.data_ptr(),
                      (__hip_bfloat16*)k_cache.data_ptr(), (__hip_bfloat16*)v_cache.data_ptr(),
                      cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), positions, rows,
-                     lengths, ws.data_ptr<float>(), uniform_pos, max_len, slots, Tmax, Hkv, J,
-                     attn_scale().c);
+                     lengths, ws.data_ptr<float>(), bt.pt, uniform_pos, max_len, slots, Tmax, Hkv,
+                     J, attn_scale().c);
   LPP_CHECK_HIP(hipGetLastError());
   launch_decode_combine<C>(ws, positions, rows, o, uniform_pos, max_len, slots, N, H, J);
 }
@@ -351,11 +372,17 @@ void launch_decode_mfma(int rep, int chunk, const at::Tensor& q, const at::Tenso
                         const at::Tensor& v_new, at::Tensor& k_cache, at::Tensor& v_cache,
                         const at::Tensor& cos_t, const at::Tensor& sin_t,
                         const int64_t* positions, const int64_t* rows, int64_t* lengths,
-                        at::Tensor& o, int uniform_pos, int max_len) {
-#define LPP_DECODE_MFMA(R, CC)                                                              \
-  if (rep == R && chunk == CC)                                                              \
-    return launch_decode_mfma_rc<R, CC>(q, k_new, v_new, k_cache, v_cache, cos_t, sin_t,    \
-                                        positions, rows, lengths, o, uniform_pos, max_len)
+                        at::Tensor& o, const DecodeTable& bt, int uniform_pos, int max_len) {
+#define LPP_DECODE_MFMA(R, CC)                                                               \
+  if (rep == R && chunk == CC) {                                                             \
+    if (bt.pt.table)                                                                         \
+      return launch_decode_mfma_rc<R, CC, true>(q, k_new, v_new, k_cache, v_cache, cos_t,    \
+                                                sin_t, positions, rows, lengths, o, bt,      \
+                                                uniform_pos, max_len);                       \
+    return launch_decode_mfma_rc<R, CC, false>(q, k_new, v_new, k_cache, v_cache, cos_t,     \
+                                               sin_t, positions, rows, lengths, o, bt,       \
+                                               uniform_pos, max_len);                        \
+  }
   LPP_DECODE_MFMA(8, 128);
   LPP_DECODE_MFMA(8, 256);
   LPP_DECODE_MFMA(8, 512);

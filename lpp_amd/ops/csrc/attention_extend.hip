@@ -51,8 +51,22 @@
 // differs in ld_tile alone: 8 bytes and the key's scale become the bf16x8 that
 // write_tile stages, exactly, so the LDS images, the tile loop, the mask, the
 // split path and the combine are the bf16 ones.
+//
+// Paged cache (attn_paged.h: a pool of 64-key pages under a block table) is the
+// template parameter PAGED of the same two kernels.  A page is one key tile
+// and every tile starts at a multiple of 64, so a tile's page id is
+// workgroup-uniform: ld_tile adds the page's base (SGPRs) where the slot
+// layout adds the row's and stays otherwise as it is.  attn_tile_pipeline
+// issues the loads of tile t + 1 a whole compute phase ahead, and a table
+// load in front of them would put its latency on that path; so the entry of
+// tile t + 1 is fetched (one scalar load) together with the global loads of
+// tile t and is long there when ld_tile comes for it.  The key index is
+// clamped to p + len - 1 before the lookup, as for the loads themselves.  The
+// append looks up the page of its own token: a chunk that crosses a page
+// boundary lands in two pages.
 #include "attention.h"
 #include "attn_fp8.h"
+#include "attn_paged.h"
 
 namespace lpp {
 
@@ -104,7 +118,7 @@ __device__ __forceinline__ unsigned short ae_bf16_bits(float x) {
 // FP8: the 8 lanes of a head (consecutive idx, so one iteration and one aligned
 // lane group) reduce the row's amax with three xor shuffles; V rows are work
 // items of the same loop, unrotated.
-template <bool FP8>
+template <bool FP8, bool PAGED>
 __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_extend_append_kernel(
     const short* __restrict__ q,      // [N,Sq,H,128]
     const short* __restrict__ k_new,  // [N,Sq,Hkv,128]
@@ -118,6 +132,7 @@ __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_e
     const int64_t* __restrict__ positions, const int64_t* __restrict__ q_lens,
     const int64_t* __restrict__ rows, int64_t* lengths,
     short* __restrict__ q_rot,        // [N,Sq,H,128]
+    PageTable pt,                     // PAGED: the caches are the pool, slots the table's rows
     int uniform_pos, int max_len, int slots, int Tmax, int Sq, int H, int Hkv) {
   constexpr int HALF = ATTN_D / 2;
   const int i = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
@@ -135,7 +150,9 @@ __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_e
   const int pos = row.p + i;                       // < max_len <= min(Tmax, Smax)
   const short* kt = k_new + tok * Hkv * ATTN_D;
   const short* vt = v_new + tok * Hkv * ATTN_D;
-  const int64_t dst = ((row.r * Tmax + pos) * (int64_t)Hkv) * ATTN_D;
+  // kv head 0 of this token's row, in the slot or in the page of pos
+  const KvRun run = kv_run<PAGED>(pt, row.r, Tmax, Hkv, 0, pos);
+  const int64_t dst = run.kv + (int64_t)pos * Hkv * ATTN_D;
   const float* cr = cos_t + (int64_t)pos * HALF;
   const float* sr = sin_t + (int64_t)pos * HALF;
 
@@ -174,7 +191,9 @@ __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_e
     const short* src = is_q ? qt + head * ATTN_D : (is_v ? vt : kt) + hk * ATTN_D;
     const bf16x8 lo = *reinterpret_cast<const bf16x8*>(src + oct * 8);
     const bf16x8 hi = *reinterpret_cast<const bf16x8*>(src + HALF + oct * 8);
-    [[maybe_unused]] const int64_t so = (row.r * Hkv + hk) * (int64_t)Tmax + pos;  // scale
+    // scale of (kv head hk, pos): kv heads are a page or a row apart
+    [[maybe_unused]] const int64_t so = run.scale + hk * (int64_t)Tmax + pos;
+    if (!is_q && !run.ok) continue;  // a table entry outside the pool: not stored
     if constexpr (FP8) {
       if (is_v) {
         store_row_fp8(lo, hi, v_cache + dst + hk * ATTN_D, v_scale + so, oct);
@@ -206,7 +225,7 @@ __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_e
     *reinterpret_cast<bf16x8*>(out + HALF + oct * 8) = ohi;
   }
   if constexpr (!FP8)
-    for (int idx = tid; idx < Hkv * (ATTN_D / 8); idx += kExtendAppendThreads)
+    for (int idx = tid; run.ok && idx < Hkv * (ATTN_D / 8); idx += kExtendAppendThreads)
       reinterpret_cast<bf16x8*>(v_cache + dst)[idx] = reinterpret_cast<const bf16x8*>(vt)[idx];
   if (lengths && i == 0 && tid == 0) lengths[row.r] = (int64_t)row.p + row.len;
 }
@@ -214,7 +233,7 @@ __global__ __launch_bounds__(kExtendAppendThreads) LPP_NO_PACKED_F32 void attn_e
 // ---- attention ------------------------------------------------------------------
 // grid (row blocks, chunks (1 when !SPLIT), N * Hkv), 512 threads, heaviest
 // row block first.  2 waves/SIMD = one 512-thread workgroup per CU.
-template <int REP, bool SPLIT, bool FP8>
+template <int REP, bool SPLIT, bool FP8, bool PAGED>
 __global__ __launch_bounds__(512, 2) LPP_NO_PACKED_F32 void attn_extend_kernel(
     const short* __restrict__ Qr,  // q_rot [N,Sq,H,128]
     const std::conditional_t<FP8, uint8_t, short>* __restrict__ Kc,  // [slots,Tmax,Hkv,128]
@@ -225,8 +244,8 @@ __global__ __launch_bounds__(512, 2) LPP_NO_PACKED_F32 void attn_extend_kernel(
     float* __restrict__ WsO,       // [N*Hkv,J,R,128] fp32     (SPLIT)
     float* __restrict__ WsML,      // [N*Hkv,J,R,2]: m, l      (SPLIT)
     const int64_t* __restrict__ positions, const int64_t* __restrict__ q_lens,
-    const int64_t* __restrict__ rows, int uniform_pos, int max_len, int slots, int Tmax,
-    int Sq, int Hkv, int J, int C, float c /* scale*log2e */) {
+    const int64_t* __restrict__ rows, PageTable pt, int uniform_pos, int max_len, int slots,
+    int Tmax, int Sq, int Hkv, int J, int C, float c /* scale*log2e */) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto k_lds = [&](int buf) -> char* { return attn_img(smem, AE_K, buf); };
   auto v_lds = [&](int buf) -> char* { return attn_img(smem, AE_V, buf); };
@@ -298,14 +317,26 @@ __global__ __launch_bounds__(512, 2) LPP_NO_PACKED_F32 void attn_extend_kernel(
   const int st_r = (lane >> 4);
   const int st_c = 8 * (lane & 15);
   const int st_off[2] = {attn_stage_off<32>(wid, 0, lane), attn_stage_off<32>(wid, 1, lane)};
-  const int64_t kv_base = ((row.r * Tmax) * (int64_t)Hkv + hkv) * ATTN_D;  // key 0
+  // key 0 of the row; PAGED: of the page of the tile ld_tile loads (run_cur) and
+  // of the tile it will be asked for next (run_nxt), which is one tile on.  This
+  // leans on attn_tile_pipeline's order of ld calls, stated at its definition.
+  KvRun run_cur = kv_run<PAGED>(pt, row.r, Tmax, Hkv, hkv, kv_begin);
+  [[maybe_unused]] KvRun run_nxt = run_cur;
 
   auto ld_tile = [&](int kv0, int pass, bf16x8& kreg, bf16x8& vreg) {
+    if constexpr (PAGED) {
+      if (pass == 0) {
+        // tiles come in order (attn_tile_pipeline): take the entry fetched with
+        // the tile before, fetch the next one alongside this tile's loads
+        run_cur = run_nxt;
+        run_nxt = kv_run<PAGED>(pt, row.r, Tmax, Hkv, hkv, min(kv0 + AE_KVB, kv_last));
+      }
+    }
     const int key = min(kv0 + stage_row(wid, pass, st_r), kv_last);
-    const int64_t rb = kv_base + (int64_t)key * sHkvD + st_c;
+    const int64_t rb = run_cur.kv + (int64_t)key * sHkvD + st_c;
     if constexpr (FP8) {
       // the same 8 dims as 8 bytes, times the key's scale: exact in bf16
-      const int64_t so = (row.r * Hkv + hkv) * (int64_t)Tmax + key;
+      const int64_t so = run_cur.scale + key;
       const uint2 kb = *reinterpret_cast<const uint2*>(&Kc[rb]);
       const uint2 vb = *reinterpret_cast<const uint2*>(&Vc[rb]);
       kreg = fp8x8_to_bf16(kb.x, kb.y, Ks[so]);
@@ -502,21 +533,23 @@ __global__ __launch_bounds__(ATTN_D) LPP_NO_PACKED_F32 void attn_extend_combine_
 // 2) and 207 (REP 4, 8) for SPLIT=true; all ScratchSize 0, 2 waves/SIMD, 64 KB
 // LDS, and the same figures for the FP8 instantiations (the conversion needs no
 // register the bf16 load did not hold).  Append 48 VGPRs (FP8: 65), combine 12,
-// no LDS, no scratch.  The three kernels
+// no LDS, no scratch.  PAGED: 205 for SPLIT=false, 207 (REP 1, 2) and 208
+// (REP 4, 8) for SPLIT=true, bf16 and FP8 alike, 6 to 9 more SGPRs (the two
+// page bases), ScratchSize 0, 2 waves/SIMD; append 48 (FP8: 62).  The three kernels
 // are LPP_NO_PACKED_F32: with packed fp32 the compiler pairs fp32 operations
 // into v_pk_* instructions (274 in this file) and takes 208 / 210 VGPRs
 // (append 58, combine 14) for the same arithmetic.  Nothing fails
 // with packed fp32 on; the figures of profiles/README.md, Round 11, are of
 // this machine code, and the packed form was not timed.
-template <int REP, bool FP8>
+template <int REP, bool FP8, bool PAGED>
 static void launch_extend(const at::Tensor& q_rot, const at::Tensor& k_cache,
                           const at::Tensor& v_cache, const float* k_scale,
                           const float* v_scale, at::Tensor& o, const int64_t* positions,
-                          const int64_t* q_lens, const int64_t* rows, int uniform_pos,
-                          int max_len, int C, bool split) {
+                          const int64_t* q_lens, const int64_t* rows, const PageTable& pt,
+                          int slots, int uniform_pos, int max_len, int C, bool split) {
   const int N = q_rot.size(0), Sq = q_rot.size(1), H = q_rot.size(2);
   const int Hkv = H / REP, R = Sq * REP;
-  const int slots = k_cache.size(0), Tmax = k_cache.size(1);
+  const int Tmax = k_cache.size(1);
   const int nblk = (R + AE_QB - 1) / AE_QB;
   auto stream = current_stream();
   const short* qp = (const short*)q_rot.data_ptr();
@@ -525,9 +558,9 @@ static void launch_extend(const at::Tensor& q_rot, const at::Tensor& k_cache,
   const cache_t* vp = (const cache_t*)v_cache.data_ptr();
   const float c = attn_scale().c;
   if (!split) {
-    hipLaunchKernelGGL((attn_extend_kernel<REP, false, FP8>), dim3(nblk, 1, N * Hkv),
+    hipLaunchKernelGGL((attn_extend_kernel<REP, false, FP8, PAGED>), dim3(nblk, 1, N * Hkv),
                        dim3(512), AE_LDS_BYTES, stream, qp, kp, vp, k_scale, v_scale,
-                       (short*)o.data_ptr(), nullptr, nullptr, positions, q_lens, rows,
+                       (short*)o.data_ptr(), nullptr, nullptr, positions, q_lens, rows, pt,
                        uniform_pos, max_len, slots, Tmax, Sq, Hkv, 1, 0, c);
     LPP_CHECK_HIP(hipGetLastError());
     return;
@@ -536,9 +569,9 @@ static void launch_extend(const at::Tensor& q_rot, const at::Tensor& k_cache,
   TORCH_CHECK(J <= 65535, "attention_extend: too many key chunks");
   auto ws_o = at::empty({(int64_t)N * Hkv, J, R, ATTN_D}, q_rot.options().dtype(at::kFloat));
   auto ws_ml = at::empty({(int64_t)N * Hkv, J, R, 2}, q_rot.options().dtype(at::kFloat));
-  hipLaunchKernelGGL((attn_extend_kernel<REP, true, FP8>), dim3(nblk, J, N * Hkv), dim3(512),
-                     AE_LDS_BYTES, stream, qp, kp, vp, k_scale, v_scale, nullptr,
-                     ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), positions, q_lens, rows,
+  hipLaunchKernelGGL((attn_extend_kernel<REP, true, FP8, PAGED>), dim3(nblk, J, N * Hkv),
+                     dim3(512), AE_LDS_BYTES, stream, qp, kp, vp, k_scale, v_scale, nullptr,
+                     ws_o.data_ptr<float>(), ws_ml.data_ptr<float>(), positions, q_lens, rows, pt,
                      uniform_pos, max_len, slots, Tmax, Sq, Hkv, J, C, c);
   LPP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(attn_extend_combine_kernel, dim3(R, N * Hkv), dim3(ATTN_D), 0, stream,
@@ -561,8 +594,10 @@ static int64_t extend_chunk(int64_t chunk) {
   return chunk;
 }
 
-// attention_extend (FP8 = false, no scales) and attention_extend_fp8.
-template <bool FP8>
+// attention_extend (FP8 = false, no scales) and attention_extend_fp8; PAGED
+// with a block table (int32 [table_rows, max_pages]: the caches are a pool of
+// 64-key pages and rows / lengths / N count table rows).
+template <bool FP8, bool PAGED>
 static at::Tensor extend(const char* who, const at::Tensor& q, const at::Tensor& k_new,
                          const at::Tensor& v_new, at::Tensor& k_cache, at::Tensor& v_cache,
                          at::Tensor* k_scale, at::Tensor* v_scale, const at::Tensor& cos_t,
@@ -570,7 +605,8 @@ static at::Tensor extend(const char* who, const at::Tensor& q, const at::Tensor&
                          const c10::optional<at::Tensor>& q_lens,
                          const c10::optional<at::Tensor>& rows,
                          const c10::optional<at::Tensor>& lengths, int64_t uniform_pos,
-                         int64_t max_len, int64_t chunk, int64_t split) {
+                         int64_t max_len, int64_t chunk, int64_t split,
+                         const c10::optional<at::Tensor>& block_table) {
   using cache_t = std::conditional_t<FP8, uint8_t, short>;
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, who, ": bf16 CUDA q required");
   TORCH_CHECK(q.dim() == 4 && q.size(1) >= 1 && q.size(3) == ATTN_D, who,
@@ -598,9 +634,34 @@ static at::Tensor extend(const char* who, const at::Tensor& q, const at::Tensor&
                     t->dim() == 2 && t->size(1) == ATTN_D / 2 && t->device() == q.device(),
                 who, ": cos/sin must be contiguous fp32 [Smax,64]");
   TORCH_CHECK(cos_t.size(0) == sin_t.size(0), who, ": cos/sin length mismatch");
-  const int64_t slots = k_cache.size(0), Tmax = k_cache.size(1);
-  TORCH_CHECK(max_len >= 1 && max_len <= Tmax && max_len <= cos_t.size(0), who,
-              ": max_len ", max_len, " must be in [1, min(Tmax, rope table)]");
+  const int64_t Tmax = k_cache.size(1);
+  int64_t slots = k_cache.size(0), row_tokens = Tmax;  // rows of the cache, tokens of a row
+  PageTable pt{nullptr, 0, 0};
+  if constexpr (PAGED) {
+    const at::Tensor& t = *block_table;
+    TORCH_CHECK(Tmax == kPageTokens, who, ": a paged cache is [num_pages,", kPageTokens,
+                ",Hkv,128], got ", Tmax, " tokens per page");
+    TORCH_CHECK(t.is_cuda() && t.device() == q.device() && t.scalar_type() == at::kInt &&
+                    t.is_contiguous() && t.dim() == 2 && t.size(0) >= 1 && t.size(1) >= 1,
+                who, ": block_table must be a contiguous int32 [table_rows,max_pages] on q's "
+                     "device");
+    TORCH_CHECK(slots >= 1 && slots < ((int64_t)1 << 31) / kPageTokens &&
+                    t.size(0) < ((int64_t)1 << 31) && t.size(1) < ((int64_t)1 << 31) / kPageTokens,
+                who, ": pool or block_table out of range");
+    pt = PageTable{t.data_ptr<int>(), (int)t.size(1), (int)slots};
+    slots = t.size(0);
+    row_tokens = t.size(1) * kPageTokens;
+    // read by every launch while the append writes the caches and lengths
+    std::vector<const at::Tensor*> written = {&k_cache, &v_cache};
+    if (lengths.has_value()) written.push_back(&lengths.value());
+    if constexpr (FP8) written.insert(written.end(), {k_scale, v_scale});
+    for (const at::Tensor* u : written)
+      TORCH_CHECK(lpp::extend_disjoint(t.data_ptr(), t.nbytes(), u->data_ptr(), u->nbytes()), who,
+                  ": block_table must not alias lengths, the scales or the caches");
+  }
+  TORCH_CHECK(max_len >= 1 && max_len <= row_tokens && max_len <= cos_t.size(0), who,
+              ": max_len ", max_len, " must be in [1, min(", PAGED ? "max_pages * 64" : "Tmax",
+              ", rope table)]");
   TORCH_CHECK(k_cache.numel() < ((int64_t)1 << 40) && q.numel() < ((int64_t)1 << 40) &&
                   N <= 65535 && N * Hkv <= 65535 && Sq * H < ((int64_t)1 << 30),
               who, ": shape out of range");  // grid y/z limits; 64-bit offsets beyond
@@ -642,7 +703,7 @@ static at::Tensor extend(const char* who, const at::Tensor& q, const at::Tensor&
   if constexpr (FP8) {
     for (const at::Tensor* t : {k_scale, v_scale}) {
       TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kFloat &&
-                      t->is_contiguous() && t->dim() == 3 && t->size(0) == slots &&
+                      t->is_contiguous() && t->dim() == 3 && t->size(0) == k_cache.size(0) &&
                       t->size(1) == Hkv && t->size(2) == Tmax,
                   who, ": k_scale/v_scale must be contiguous fp32 [slots,Hkv,Tmax] on q's device");
       // written by the append while later launches read every other argument
@@ -670,12 +731,12 @@ static at::Tensor extend(const char* who, const at::Tensor& q, const at::Tensor&
               ": H/Hkv must be 1, 2, 4 or 8, got ", rep);  // before the cache is written
 
   auto q_rot = at::empty_like(q);
-  hipLaunchKernelGGL(lpp::attn_extend_append_kernel<FP8>, dim3((unsigned)Sq, (unsigned)N),
+  hipLaunchKernelGGL((lpp::attn_extend_append_kernel<FP8, PAGED>), dim3((unsigned)Sq, (unsigned)N),
                      dim3(lpp::kExtendAppendThreads), 0, lpp::current_stream(),
                      (const short*)q.data_ptr(), (const short*)k_new.data_ptr(),
                      (const short*)v_new.data_ptr(), (cache_t*)k_cache.data_ptr(),
                      (cache_t*)v_cache.data_ptr(), ksp, vsp, cos_t.data_ptr<float>(),
-                     sin_t.data_ptr<float>(), pp, qp, rp, lp, (short*)q_rot.data_ptr(),
+                     sin_t.data_ptr<float>(), pp, qp, rp, lp, (short*)q_rot.data_ptr(), pt,
                      (int)uniform_pos, (int)max_len, (int)slots, (int)Tmax, (int)Sq, (int)H,
                      (int)Hkv);
   LPP_CHECK_HIP(hipGetLastError());
@@ -683,8 +744,9 @@ static at::Tensor extend(const char* who, const at::Tensor& q, const at::Tensor&
   const bool do_split = split < 0 ? Sq * rep < lpp::kExtendSplitRows : split == 1;
 #define LPP_EXTEND_REP(RR)                                                                  \
   case RR:                                                                                  \
-    lpp::launch_extend<RR, FP8>(q_rot, k_cache, v_cache, ksp, vsp, o, pp, qp, rp,           \
-                                (int)uniform_pos, (int)max_len, (int)C, do_split);          \
+    lpp::launch_extend<RR, FP8, PAGED>(q_rot, k_cache, v_cache, ksp, vsp, o, pp, qp, rp,    \
+                                       pt, (int)slots, (int)uniform_pos, (int)max_len,      \
+                                       (int)C, do_split);                                   \
     break
   switch (rep) {
     LPP_EXTEND_REP(1);
@@ -709,15 +771,22 @@ int64_t attention_extend_chunk(int64_t chunk) { return lpp::extend_chunk(chunk);
 // scripts/extend_bench.py).  split: -1 = by the row count (Sq * H/Hkv below
 // kExtendSplitRows), 0 / 1 force the direct / the split path.  Results differ
 // in the last bits between chunk sizes and paths, never between calls of one.
+// block_table: the paged layout (attn_paged.h); the same paths and bits.
 at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
                             at::Tensor sin_t, c10::optional<at::Tensor> positions,
                             c10::optional<at::Tensor> q_lens, c10::optional<at::Tensor> rows,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                            int64_t max_len, int64_t chunk, int64_t split) {
-  return lpp::extend<false>("attention_extend", q, k_new, v_new, k_cache, v_cache, nullptr,
-                            nullptr, cos_t, sin_t, positions, q_lens, rows, lengths, uniform_pos,
-                            max_len, chunk, split);
+                            int64_t max_len, int64_t chunk, int64_t split,
+                            c10::optional<at::Tensor> block_table) {
+  const char* who = "attention_extend";
+  if (block_table.has_value())
+    return lpp::extend<false, true>(who, q, k_new, v_new, k_cache, v_cache, nullptr, nullptr,
+                                    cos_t, sin_t, positions, q_lens, rows, lengths, uniform_pos,
+                                    max_len, chunk, split, block_table);
+  return lpp::extend<false, false>(who, q, k_new, v_new, k_cache, v_cache, nullptr, nullptr,
+                                   cos_t, sin_t, positions, q_lens, rows, lengths, uniform_pos,
+                                   max_len, chunk, split, block_table);
 }
 
 // The same over e4m3 caches with per-(slot, kv head, token) scales.
@@ -728,8 +797,14 @@ at::Tensor attention_extend_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new
                                 c10::optional<at::Tensor> q_lens,
                                 c10::optional<at::Tensor> rows,
                                 c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                                int64_t max_len, int64_t chunk, int64_t split) {
-  return lpp::extend<true>("attention_extend_fp8", q, k_new, v_new, k_cache, v_cache, &k_scale,
-                           &v_scale, cos_t, sin_t, positions, q_lens, rows, lengths, uniform_pos,
-                           max_len, chunk, split);
+                                int64_t max_len, int64_t chunk, int64_t split,
+                                c10::optional<at::Tensor> block_table) {
+  const char* who = "attention_extend_fp8";
+  if (block_table.has_value())
+    return lpp::extend<true, true>(who, q, k_new, v_new, k_cache, v_cache, &k_scale, &v_scale,
+                                   cos_t, sin_t, positions, q_lens, rows, lengths, uniform_pos,
+                                   max_len, chunk, split, block_table);
+  return lpp::extend<true, false>(who, q, k_new, v_new, k_cache, v_cache, &k_scale, &v_scale,
+                                  cos_t, sin_t, positions, q_lens, rows, lengths, uniform_pos,
+                                  max_len, chunk, split, block_table);
 }

@@ -229,6 +229,9 @@ __device__ __forceinline__ bf16x8 pack_frag16(const float p[2][4], int hi4_odd) 
 // they go to the other buffer, which every wave left at the barrier before.
 // The barrier sits outside every wave condition of the body.  The forward and
 // dK/dV call this; dQ writes the same steps out (see attention_bwd.hip).
+// Order of ld calls, which callers may rely on (the paged extend kernel looks
+// up the next tile's page in ld): tiles in ascending order from begin, each
+// tile exactly once, pass 0 immediately followed by pass 1 of the same tile.
 template <int STEP, class Ld, class Write, class Body>
 __device__ __forceinline__ void attn_tile_pipeline(int begin, int end, Ld ld, Write write,
                                                    Body body) {

@@ -45,21 +45,24 @@ at::Tensor attention_decode(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor sin_t, c10::optional<at::Tensor> positions,
                             c10::optional<at::Tensor> rows,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                            int64_t max_len, int64_t chunk, int64_t impl);
+                            int64_t max_len, int64_t chunk, int64_t impl,
+                            c10::optional<at::Tensor> block_table);
 at::Tensor attention_decode_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                                 at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale,
                                 at::Tensor v_scale, at::Tensor cos_t, at::Tensor sin_t,
                                 c10::optional<at::Tensor> positions,
                                 c10::optional<at::Tensor> rows,
                                 c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                                int64_t max_len, int64_t chunk);
+                                int64_t max_len, int64_t chunk,
+                                c10::optional<at::Tensor> block_table);
 int64_t attention_decode_chunk();
 at::Tensor attention_extend(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                             at::Tensor k_cache, at::Tensor v_cache, at::Tensor cos_t,
                             at::Tensor sin_t, c10::optional<at::Tensor> positions,
                             c10::optional<at::Tensor> q_lens, c10::optional<at::Tensor> rows,
                             c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                            int64_t max_len, int64_t chunk, int64_t split);
+                            int64_t max_len, int64_t chunk, int64_t split,
+                            c10::optional<at::Tensor> block_table);
 at::Tensor attention_extend_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new,
                                 at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale,
                                 at::Tensor v_scale, at::Tensor cos_t, at::Tensor sin_t,
@@ -67,7 +70,8 @@ at::Tensor attention_extend_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new
                                 c10::optional<at::Tensor> q_lens,
                                 c10::optional<at::Tensor> rows,
                                 c10::optional<at::Tensor> lengths, int64_t uniform_pos,
-                                int64_t max_len, int64_t chunk, int64_t split);
+                                int64_t max_len, int64_t chunk, int64_t split,
+                                c10::optional<at::Tensor> block_table);
 int64_t attention_extend_chunk(int64_t chunk);
 at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B);
 void wgrad_f32_accum(at::Tensor x, at::Tensor dy, at::Tensor dw);
@@ -144,18 +148,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_decode", &attention_decode,
         "fused single-token decode: RoPE + KV-cache write + GQA attention over keys 0..p of "
         "each row's cache row -> o [N,1,H,128]; chunk 0 = the compiled-in chunk size; impl 0 = "
-        "kernel by H/Hkv, 1 = vector ALU (H/Hkv <= 8), 2 = MFMA (H/Hkv 8 or 16)",
+        "kernel by H/Hkv, 1 = vector ALU (H/Hkv <= 8), 2 = MFMA (H/Hkv 8 or 16); block_table "
+        "int32 [table_rows,max_pages]: the caches are a pool [num_pages,64,Hkv,128]",
         py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("cos"), py::arg("sin"), py::arg("positions"),
         py::arg("rows"), py::arg("lengths"), py::arg("uniform_pos"), py::arg("max_len"),
-        py::arg("chunk") = 0, py::arg("impl") = 0);
+        py::arg("chunk") = 0, py::arg("impl") = 0, py::arg("block_table") = py::none());
   m.def("attention_decode_fp8", &attention_decode_fp8,
         "attention_decode over e4m3 caches [slots,Tmax,Hkv,128] with power-of-two fp32 scales "
         "k_scale / v_scale [slots,Hkv,Tmax]; one MFMA kernel for H/Hkv 1, 2, 4, 8 and 16",
         py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cos"),
         py::arg("sin"), py::arg("positions"), py::arg("rows"), py::arg("lengths"),
-        py::arg("uniform_pos"), py::arg("max_len"), py::arg("chunk") = 0);
+        py::arg("uniform_pos"), py::arg("max_len"), py::arg("chunk") = 0,
+        py::arg("block_table") = py::none());
   m.def("attention_decode_chunk", &attention_decode_chunk,
         "keys per workgroup of attention_decode");
   m.def("attention_extend", &attention_extend,
@@ -165,7 +171,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("cos"), py::arg("sin"), py::arg("positions"),
         py::arg("q_lens"), py::arg("rows"), py::arg("lengths"), py::arg("uniform_pos"),
-        py::arg("max_len"), py::arg("chunk") = 0, py::arg("split") = -1);
+        py::arg("max_len"), py::arg("chunk") = 0, py::arg("split") = -1,
+        py::arg("block_table") = py::none());
   m.def("attention_extend_fp8", &attention_extend_fp8,
         "attention_extend over e4m3 caches with k_scale / v_scale as for attention_decode_fp8: "
         "the append quantises each K and V row, the attention kernel dequantises into LDS",
@@ -173,7 +180,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cos"),
         py::arg("sin"), py::arg("positions"), py::arg("q_lens"), py::arg("rows"),
         py::arg("lengths"), py::arg("uniform_pos"), py::arg("max_len"), py::arg("chunk") = 0,
-        py::arg("split") = -1);
+        py::arg("split") = -1, py::arg("block_table") = py::none());
   m.def("attention_extend_chunk", &attention_extend_chunk,
         "keys per split workgroup of attention_extend (chunk: 0 or a checked override)",
         py::arg("chunk") = 0);

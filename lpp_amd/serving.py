@@ -55,7 +55,9 @@ class ContinuousBatchingEngine:
                  eos_token_id: Optional[int] = None,
                  generator: Optional[torch.Generator] = None,
                  prefill_chunk: Optional[int] = None,
-                 kv_dtype: Optional[torch.dtype] = None):
+                 kv_dtype: Optional[torch.dtype] = None,
+                 kv_page_size: Optional[int] = None,
+                 kv_pages: Optional[int] = None):
         """``prefill_chunk``: None admits as before (equal-length prompts
         prefill together, each in one piece).  A value admits prompts of any
         lengths together and prefills them at most that many tokens per row
@@ -66,9 +68,24 @@ class ContinuousBatchingEngine:
         ``torch.float8_e4m3fn`` (opt-in) halves its bytes: e4m3 rows with one
         power-of-two scale per (slot, kv head, token), see ``RaggedKVCache``.
         It needs ``prefill_chunk``, because the one-piece admission writes the
-        cache without quantising."""
+        cache without quantising.
+
+        ``kv_page_size`` with ``kv_pages`` (opt-in) pages the cache: every
+        layer's K/V is a pool of ``kv_pages`` pages of ``kv_page_size`` tokens
+        and one block table, shared by all layers, names each slot's pages.  A
+        request waits until ``ceil((prompt + max_new_tokens) / kv_page_size)``
+        pages are free, holds them until it finishes, and is rejected at
+        ``submit`` if it asks for more than ``kv_pages``.  How many requests
+        fit is then decided by the tokens they hold, not by ``max_seq_len``
+        per slot.  It needs ``prefill_chunk`` for the reason fp8 does; the
+        gfx950 kernels serve a page of 64 tokens."""
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
+        if (kv_page_size is None) != (kv_pages is None):
+            raise ValueError("kv_page_size and kv_pages go together")
+        if kv_page_size is not None and prefill_chunk is None:
+            raise ValueError("a paged KV cache needs prefill_chunk: the one-piece admission "
+                             "writes the cache contiguously")
         if kv_dtype is torch.float8_e4m3fn and prefill_chunk is None:
             raise ValueError("an fp8 KV cache needs prefill_chunk: only the chunked prefill "
                              "(ops.extend_attention) quantises what it appends")
@@ -86,9 +103,19 @@ class ContinuousBatchingEngine:
         self.decoders = [l for l in model.layers if isinstance(l, DecoderLayerPipe)]
         self.caches = [
             RaggedKVCache(max_slots, max_seq_len, cfg.kv_heads, cfg.head_dim,
-                          self.device, p.dtype, kv_dtype=kv_dtype)
+                          self.device, p.dtype, kv_dtype=kv_dtype,
+                          page_size=kv_page_size, num_pages=kv_pages)
             for _ in self.decoders
         ]
+        self.kv_page_size = kv_page_size
+        self.kv_pages = kv_pages
+        self.free_pages: deque[int] = deque(range(kv_pages or 0))
+        self.slot_pages: Dict[int, List[int]] = {}  # slot -> the pages it holds
+        self.block_table = None
+        if kv_page_size is not None:
+            self.block_table = self.caches[0].block_table
+            for c in self.caches:
+                c.block_table = self.block_table  # one table for every layer
         self.free_slots = deque(range(max_slots))
         self.active: Dict[int, Request] = {}  # slot -> request
         self.waiting: deque[Request] = deque()
@@ -102,7 +129,14 @@ class ContinuousBatchingEngine:
                 f"request {req.uid}: prompt+new "
                 f"{req.prompt.numel() + req.max_new_tokens} > max_seq_len "
                 f"{self.max_seq_len}")
+        if self.block_table is not None and self._pages_needed(req) > self.kv_pages:
+            raise ValueError(
+                f"request {req.uid}: needs {self._pages_needed(req)} KV pages, the pool has "
+                f"{self.kv_pages}")
         self.waiting.append(req)
+
+    def _pages_needed(self, req: Request) -> int:
+        return -(-(req.prompt.numel() + req.max_new_tokens) // self.kv_page_size)
 
     def pending(self) -> int:
         return len(self.waiting) + len(self.prefilling) + len(self.active)
@@ -150,7 +184,16 @@ class ContinuousBatchingEngine:
         becomes active; its first token is sampled from the logits of its
         last prompt token."""
         while self.waiting and self.free_slots:
+            if self.block_table is not None:
+                # first come, first served: the head of the queue waits for its pages
+                need = self._pages_needed(self.waiting[0])
+                if need > len(self.free_pages):
+                    break
             req, slot = self.waiting.popleft(), self.free_slots.popleft()
+            if self.block_table is not None:
+                pages = [self.free_pages.popleft() for _ in range(need)]
+                self.slot_pages[slot] = pages
+                self.block_table[slot, :need] = torch.tensor(pages, dtype=torch.int32)
             for c in self.caches:
                 c.free(slot)
             req.slot = slot
@@ -235,6 +278,7 @@ class ContinuousBatchingEngine:
                 for c in self.caches:
                     c.free(slot)
                 self.free_slots.append(slot)
+                self.free_pages.extend(self.slot_pages.pop(slot, ()))
         if not self.active:
             return done
         # one batched ragged decode over every active slot (views memoized
