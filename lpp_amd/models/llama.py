@@ -30,7 +30,7 @@ import torch.nn as nn
 from ..config import ModelConfig
 from ..layer_spec import LayerSpec
 from .. import ops
-from ..ops.linear import LPLinear, lp_linear
+from ..ops.linear import LPLinear, forward_fp8, quantize_module_fp8_, lp_linear
 
 
 class RMSNorm(nn.Module):
@@ -511,7 +511,14 @@ class LMHeadPipe(nn.Linear):
     def __init__(self, hidden_size: int, vocab_size: int):
         super().__init__(hidden_size, vocab_size, bias=False)
 
+    def quantize_fp8_(self) -> "LMHeadPipe":
+        """Hold the weight as e4m3 + block scales from now on (inference only)."""
+        quantize_module_fp8_(self)
+        return self
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.weight is None:
+            return forward_fp8(self, x)
         return lp_linear(x, self.weight)
 
     @staticmethod

@@ -103,6 +103,7 @@ from .attention import (DocLayout, causal_attention, decode_attention,  # noqa: 
                         extend_attention, extend_attention_ref,
                         extend_attention_hip_supported, FP8_KV_DTYPE,
                         quantize_kv_rows_fp8)
+from .linear import quantize_weight_fp8, linear_fp8w, linear_fp8w_ref  # noqa: E402
 
 __all__ = [
     "rmsnorm",
@@ -124,6 +125,9 @@ __all__ = [
     "extend_attention_hip_supported",
     "FP8_KV_DTYPE",
     "quantize_kv_rows_fp8",
+    "quantize_weight_fp8",
+    "linear_fp8w",
+    "linear_fp8w_ref",
     "extension",
     "use_hip",
     "force_eager",

@@ -73,6 +73,8 @@ at::Tensor attention_extend_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new
                                 int64_t max_len, int64_t chunk, int64_t split,
                                 c10::optional<at::Tensor> block_table);
 int64_t attention_extend_chunk(int64_t chunk);
+at::Tensor linear_fp8w(at::Tensor x, at::Tensor wq, at::Tensor scale);
+at::Tensor linear_fp8w_dequant(at::Tensor wq, at::Tensor scale);
 at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B);
 void wgrad_f32_accum(at::Tensor x, at::Tensor dy, at::Tensor dw);
 void wgrad_f32_accum_pre(at::Tensor xT, at::Tensor dyT, at::Tensor dw);
@@ -184,7 +186,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_extend_chunk", &attention_extend_chunk,
         "keys per split workgroup of attention_extend (chunk: 0 or a checked override)",
         py::arg("chunk") = 0);
-  m.def("wgrad_f32_accum", &wgrad_f32_accum, "dW_f32 += dY^T @ X (hipBLASLt, beta=1)");
+  m.def("linear_fp8w", &linear_fp8w,
+        "FP8 weight-only linear: bf16 x [M,in], M <= 64, times e4m3 wq [out,in] under "
+        "power-of-two fp32 scale [out,in/128] -> bf16 y [M,out], fp32 accumulation",
+        py::arg("x"), py::arg("wq"), py::arg("scale"));
+  m.def("linear_fp8w_dequant", &linear_fp8w_dequant,
+        "e4m3 wq [out,in] and fp32 scale [out,in/128] -> the bf16 weight [out,in], exactly",
+        py::arg("wq"), py::arg("scale"));
+  m.def("wgrad_f32_accum",&wgrad_f32_accum, "dW_f32 += dY^T @ X (hipBLASLt, beta=1)");
   m.def("wgrad_f32_accum_pre", &wgrad_f32_accum_pre,
         "dW_f32 += dyT @ xT^T, pre-transposed k-contiguous operands (hipBLASLt, beta=1)");
   m.def("transpose2d", &transpose2d, "bf16/fp16 [R,C] -> [C,R] LDS-tiled transpose");

@@ -15,7 +15,7 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import extension, force_eager
+from . import extension, force_eager, use_hip
 
 
 class _XTCache:
@@ -216,6 +216,91 @@ def lp_linear(x: torch.Tensor, weight: torch.nn.Parameter) -> torch.Tensor:
     return F.linear(x, weight)
 
 
+# ---------------------------------------------------------------------------
+# FP8 weight-only linear (serving).  A weight [out, in] is held as e4m3 bytes
+# and one power-of-two fp32 scale per (output row, block of 128 inputs): the
+# KV-cache rule (ops.quantize_kv_rows_fp8) applied to each block, so byte *
+# scale is exact in bf16 and the product is a bf16 GEMM over the dequantised
+# weight.  Activations stay bf16 (W8A16); csrc/linear_fp8w.hip.
+# ---------------------------------------------------------------------------
+FP8W_BLOCK = 128     # inputs per scale
+FP8W_MAX_M = 64      # rows of x the kernel serves
+
+
+def quantize_weight_fp8(w: torch.Tensor):
+    """``w [out, in]`` -> ``(wq float8_e4m3fn [out, in], scale fp32 [out,
+    in/128])``; needs ``in % 128 == 0`` and ``out % 16 == 0``."""
+    from .attention import quantize_kv_rows_fp8
+
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_fp8: weight must be [out, in], got {tuple(w.shape)}")
+    out, inn = w.shape
+    if inn % FP8W_BLOCK or out % 16:
+        raise ValueError(f"quantize_weight_fp8: needs in % {FP8W_BLOCK} == 0 and out % 16 == 0, "
+                         f"got [out, in] = [{out}, {inn}]")
+    wq, scale = quantize_kv_rows_fp8(w.reshape(out, inn // FP8W_BLOCK, FP8W_BLOCK))
+    return wq.reshape(out, inn), scale
+
+
+def _dequant_weight_ref(wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The bf16 weight of (wq, scale), exactly, in stock torch ops."""
+    out, inn = wq.shape
+    w = wq.float().view(out, inn // FP8W_BLOCK, FP8W_BLOCK) * scale[..., None]
+    return w.view(out, inn).to(torch.bfloat16)
+
+
+def linear_fp8w_ref(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``F.linear`` over the dequantised bf16 weight: the CPU path and the
+    kernel's oracle, bit for bit a model that holds the dequantised weights."""
+    return F.linear(x, _dequant_weight_ref(wq, scale).to(x.dtype))
+
+
+def linear_fp8w(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``x [..., in] @ dequant(wq, scale)^T -> [..., out]``, inference only.
+
+    On the GPU with bf16 x and at most 64 rows (decode ticks) the gfx950
+    kernel streams the e4m3 weight once; its result does not depend on how
+    many rows ride together.  Above 64 rows (prefill ticks, whole-prompt
+    admission) the GEMM is compute-bound and stays on hipBLASLt: the weight
+    is dequantised into a scratch tensor by ``linear_fp8w_dequant`` and
+    ``F.linear`` runs over it.  On the CPU or under ``LPP_FORCE_EAGER`` it is
+    ``linear_fp8w_ref``."""
+    if not use_hip(x):
+        return linear_fp8w_ref(x, wq, scale)
+    if x.dtype is not torch.bfloat16:
+        raise ValueError(f"linear_fp8w: the gfx950 kernel takes bf16 x, got {x.dtype}")
+    ext = extension()
+    if x.dim() < 1 or x.shape[-1] != wq.shape[1]:
+        raise ValueError(f"linear_fp8w: x [..., {x.shape[-1] if x.dim() else '?'}] against a "
+                         f"weight [out, in] = {tuple(wq.shape)}")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, x.shape[-1])
+    if x2.shape[0] == 0:
+        return x.new_empty(*lead, wq.shape[0])
+    if x2.shape[0] <= FP8W_MAX_M:
+        y = ext.linear_fp8w(x2, wq, scale)   # raises on a non-contiguous x
+    else:
+        y = F.linear(x2, ext.linear_fp8w_dequant(wq, scale))
+    return y.view(*lead, wq.shape[0])
+
+
+def quantize_module_fp8_(mod: torch.nn.Module) -> None:
+    """Replace ``mod.weight`` by the buffers ``weight_fp8`` / ``weight_scale``."""
+    if getattr(mod, "weight", None) is None:
+        return  # already quantised
+    wq, scale = quantize_weight_fp8(mod.weight.data)
+    mod.register_parameter("weight", None)   # the bf16 storage goes with its last reference
+    mod.register_buffer("weight_fp8", wq)
+    mod.register_buffer("weight_scale", scale)
+
+
+def forward_fp8(mod: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{type(mod).__name__}: fp8 weights are inference-only; call under "
+                           "torch.no_grad()")
+    return linear_fp8w(x, mod.weight_fp8, mod.weight_scale)
+
+
 class LPLinear(torch.nn.Linear):
     """Drop-in nn.Linear (bias-free) using the fused-wgrad path."""
 
@@ -223,5 +308,12 @@ class LPLinear(torch.nn.Linear):
         assert not bias, "LLaMA projections are bias-free"
         super().__init__(in_features, out_features, bias=False)
 
+    def quantize_fp8_(self) -> "LPLinear":
+        """Hold the weight as e4m3 + block scales from now on (inference only)."""
+        quantize_module_fp8_(self)
+        return self
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.weight is None:
+            return forward_fp8(self, x)
         return lp_linear(x, self.weight)

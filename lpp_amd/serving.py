@@ -34,8 +34,9 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .models.llama import (DecoderLayerPipe, GatherKVCache, MultiSlotKVCache,
+from .models.llama import (DecoderLayerPipe, GatherKVCache, LMHeadPipe, MultiSlotKVCache,
                            RaggedKVCache)
+from .ops.linear import LPLinear
 
 
 @dataclass
@@ -57,7 +58,8 @@ class ContinuousBatchingEngine:
                  prefill_chunk: Optional[int] = None,
                  kv_dtype: Optional[torch.dtype] = None,
                  kv_page_size: Optional[int] = None,
-                 kv_pages: Optional[int] = None):
+                 kv_pages: Optional[int] = None,
+                 weight_dtype: Optional[torch.dtype] = None):
         """``prefill_chunk``: None admits as before (equal-length prompts
         prefill together, each in one piece).  A value admits prompts of any
         lengths together and prefills them at most that many tokens per row
@@ -78,7 +80,17 @@ class ContinuousBatchingEngine:
         ``submit`` if it asks for more than ``kv_pages``.  How many requests
         fit is then decided by the tokens they hold, not by ``max_seq_len``
         per slot.  It needs ``prefill_chunk`` for the reason fp8 does; the
-        gfx950 kernels serve a page of 64 tokens."""
+        gfx950 kernels serve a page of 64 tokens.
+
+        ``weight_dtype``: None keeps the model's weights.
+        ``torch.float8_e4m3fn`` (opt-in) quantises every projection of the
+        decoder layers and the LM head IN PLACE (``LPLinear.quantize_fp8_``:
+        e4m3 bytes and one power-of-two scale per 128 inputs of a row, half
+        the weight memory); embedding and norms stay as they are.  Decode
+        ticks then run ``ops.linear_fp8w``.  Independent of ``kv_dtype`` and
+        paging."""
+        if weight_dtype not in (None, torch.float8_e4m3fn):
+            raise ValueError(f"weight_dtype must be None or float8_e4m3fn, got {weight_dtype}")
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         if (kv_page_size is None) != (kv_pages is None):
@@ -101,6 +113,12 @@ class ContinuousBatchingEngine:
         self.device = p.device
         cfg = model.cfg
         self.decoders = [l for l in model.layers if isinstance(l, DecoderLayerPipe)]
+        if weight_dtype is not None:
+            for layer in model.layers:
+                if isinstance(layer, (DecoderLayerPipe, LMHeadPipe)):
+                    for m in layer.modules():
+                        if isinstance(m, (LPLinear, LMHeadPipe)):
+                            m.quantize_fp8_()
         self.caches = [
             RaggedKVCache(max_slots, max_seq_len, cfg.kv_heads, cfg.head_dim,
                           self.device, p.dtype, kv_dtype=kv_dtype,

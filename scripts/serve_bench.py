@@ -38,6 +38,9 @@ def main() -> int:
                          "per tick (default: whole-prompt admission)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the e4m3 KV cache (needs --prefill-chunk)")
+    ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: e4m3 projection and LM-head weights (ops.linear_fp8w); the model "
+                         "is quantised in place, so the static run uses them too")
     args = ap.parse_args()
 
     assert torch.cuda.is_available(), "run on the GPU box"
@@ -55,7 +58,9 @@ def main() -> int:
     eng = ContinuousBatchingEngine(m, max_slots=args.slots, max_seq_len=args.max_seq,
                                    prefill_chunk=args.prefill_chunk,
                                    kv_dtype=torch.float8_e4m3fn if args.kv_dtype == "fp8"
-                                   else None)
+                                   else None,
+                                   weight_dtype=torch.float8_e4m3fn
+                                   if args.weight_dtype == "fp8" else None)
     for i, (p, n) in enumerate(zip(prompts, lens)):
         eng.submit(Request(f"r{i}", p, n))
     finish_c = {}
@@ -89,7 +94,7 @@ def main() -> int:
                  for i in range(0, args.requests, args.slots)) - total_tokens
 
     print(f"requests={args.requests} slots={args.slots} prompt={args.prompt_len} "
-          f"prefill_chunk={args.prefill_chunk} kv_dtype={args.kv_dtype} "
+          f"prefill_chunk={args.prefill_chunk} kv_dtype={args.kv_dtype} weight_dtype={args.weight_dtype} "
           f"generated={total_tokens} tokens (mixed 16..256)")
     print(f"continuous: {t_cont:.2f} s = {total_tokens / t_cont:.0f} tok/s, "
           f"mean completion latency {lat_c:.2f} s")
