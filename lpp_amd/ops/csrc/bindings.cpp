@@ -74,6 +74,7 @@ at::Tensor attention_extend_fp8(at::Tensor q, at::Tensor k_new, at::Tensor v_new
                                 c10::optional<at::Tensor> block_table);
 int64_t attention_extend_chunk(int64_t chunk);
 at::Tensor linear_fp8w(at::Tensor x, at::Tensor wq, at::Tensor scale);
+at::Tensor linear_fp8w_tiled(at::Tensor x, at::Tensor wq, at::Tensor scale, int64_t slices);
 at::Tensor linear_fp8w_dequant(at::Tensor wq, at::Tensor scale);
 at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B);
 void wgrad_f32_accum(at::Tensor x, at::Tensor dy, at::Tensor dw);
@@ -190,6 +191,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "FP8 weight-only linear: bf16 x [M,in], M <= 64, times e4m3 wq [out,in] under "
         "power-of-two fp32 scale [out,in/128] -> bf16 y [M,out], fp32 accumulation",
         py::arg("x"), py::arg("wq"), py::arg("scale"));
+  m.def("linear_fp8w_tiled", &linear_fp8w_tiled,
+        "FP8 weight-only linear for any M >= 1: 128 x 128 tiles, e4m3 dequantised on the way "
+        "into LDS; slices: 0 takes the split-K rule, 1 .. in/128 forces that many K-slices",
+        py::arg("x"), py::arg("wq"), py::arg("scale"), py::arg("slices") = 0);
   m.def("linear_fp8w_dequant", &linear_fp8w_dequant,
         "e4m3 wq [out,in] and fp32 scale [out,in/128] -> the bf16 weight [out,in], exactly",
         py::arg("wq"), py::arg("scale"));

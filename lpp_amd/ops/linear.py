@@ -255,16 +255,33 @@ def linear_fp8w_ref(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> t
     return F.linear(x, _dequant_weight_ref(wq, scale).to(x.dtype))
 
 
-def linear_fp8w(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+def _fp8w_tiled_enabled() -> bool:
+    """Above 64 rows take the tiled fp8 kernel instead of dequantise +
+    hipBLASLt.  Off by default; LPP_FP8W_TILED=1 turns it on."""
+    return os.environ.get("LPP_FP8W_TILED", "0") == "1"
+
+
+def linear_fp8w(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor,
+                tiled: bool | None = None) -> torch.Tensor:
     """``x [..., in] @ dequant(wq, scale)^T -> [..., out]``, inference only.
 
-    On the GPU with bf16 x and at most 64 rows (decode ticks) the gfx950
-    kernel streams the e4m3 weight once; its result does not depend on how
-    many rows ride together.  Above 64 rows (prefill ticks, whole-prompt
-    admission) the GEMM is compute-bound and stays on hipBLASLt: the weight
-    is dequantised into a scratch tensor by ``linear_fp8w_dequant`` and
-    ``F.linear`` runs over it.  On the CPU or under ``LPP_FORCE_EAGER`` it is
-    ``linear_fp8w_ref``."""
+    On the GPU with bf16 x and at most 64 rows (decode ticks) the skinny
+    gfx950 kernel streams the e4m3 weight once; its result does not depend on
+    how many rows ride together, and it always serves this range.  Above 64
+    rows (prefill ticks, whole-prompt admission) there are two paths:
+
+    * default: the weight is dequantised into a bf16 scratch tensor by
+      ``linear_fp8w_dequant`` and ``F.linear`` (hipBLASLt) runs over it;
+    * ``tiled=True``, or ``tiled=None`` with ``LPP_FP8W_TILED=1``: the tiled
+      gfx950 kernel (``linear_fp8w_tiled``) reads the e4m3 bytes once per
+      128-token tile and dequantises them on the way into LDS, with no bf16
+      copy of the weight.  It splits K by a rule of (in, out, number of
+      token tiles), so the same call returns the same bits every time, but
+      the bits of a row may depend on how many rows ride along, as they may
+      on the hipBLASLt path.
+
+    ``tiled=False`` forces the default path.  On the CPU or under
+    ``LPP_FORCE_EAGER`` the op is ``linear_fp8w_ref`` whatever ``tiled`` says."""
     if not use_hip(x):
         return linear_fp8w_ref(x, wq, scale)
     if x.dtype is not torch.bfloat16:
@@ -279,6 +296,8 @@ def linear_fp8w(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch
         return x.new_empty(*lead, wq.shape[0])
     if x2.shape[0] <= FP8W_MAX_M:
         y = ext.linear_fp8w(x2, wq, scale)   # raises on a non-contiguous x
+    elif _fp8w_tiled_enabled() if tiled is None else tiled:
+        y = ext.linear_fp8w_tiled(x2, wq, scale, 0)
     else:
         y = F.linear(x2, ext.linear_fp8w_dequant(wq, scale))
     return y.view(*lead, wq.shape[0])

@@ -7,6 +7,13 @@ than the last-level cache (--ring-mb), so every call streams its weight from
 HBM as a decode tick does; the two paths alternate inside one run.  TB/s counts
 the weight bytes alone (1 byte + 4/128 per element for fp8, 2 for bf16).
 
+A second table (--tiled-ms, rows above 64) times three paths per point, in
+--rounds alternating rounds: bf16 F.linear, dequantise + F.linear (the default
+route of ops.linear_fp8w above 64 rows) and the tiled fp8 kernel.  Each time is
+the mean over the rounds; the ratio of the tiled kernel against dequantise +
+F.linear is given with its lowest and highest value over the rounds, each
+round's ratio taken from that round's own two timings.
+
 Usage (GPU box):  python scripts/linear_fp8w_bench.py [--reps 20]
 """
 
@@ -51,13 +58,19 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--ring-mb", type=int, default=768)
-    ap.add_argument("--ms", type=int, nargs="+", default=[1, 8, 16, 64])
+    ap.add_argument("--ms", type=int, nargs="*", default=[1, 8, 16, 64])
+    ap.add_argument("--tiled-ms", type=int, nargs="*", default=[65, 128, 256, 512, 1024, 2048])
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--shapes", nargs="*", default=None, help="names to keep (default all)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "run on the GPU box"
     g = torch.Generator().manual_seed(0)
-    print("| shape | in x out | M | bf16 F.linear us | TB/s | fp8w us | TB/s | speedup |")
-    print("|---|---|---|---|---|---|---|---|")
-    for name, inn, out in SHAPES:
+    shapes = [sh for sh in SHAPES if args.shapes is None or sh[0] in args.shapes]
+    if args.ms:
+        print("| shape | in x out | M | bf16 F.linear us | TB/s | fp8w us | TB/s | speedup |")
+        print("|---|---|---|---|---|---|---|---|")
+    tiled_rows = []
+    for name, inn, out in shapes:
         w = (torch.randn(out, inn, generator=g) * 0.02).bfloat16().cuda()
         wq, sc = ops.quantize_weight_fp8(w)
         n = max(2, -(-args.ring_mb * 2**20 // (2 * inn * out)))
@@ -73,7 +86,25 @@ def main() -> int:
             tb_q = (inn * out + 4 * inn * out // 128) / ms_q / 1e9
             print(f"| {name} | {inn} x {out} | {M} | {ms_bf * 1e3:.1f} | {tb_bf:.2f} | "
                   f"{ms_q * 1e3:.1f} | {tb_q:.2f} | {ms_bf / ms_q:.2f}x |", flush=True)
+        for M in args.tiled_ms:
+            x = (torch.randn(M, inn, generator=g)).bfloat16().cuda()
+            paths = [(lambda t: F.linear(x, t), ring_bf),
+                     (lambda t: ops.linear_fp8w(x, *t, tiled=False), ring_q),
+                     (lambda t: ops.linear_fp8w(x, *t, tiled=True), ring_q)]
+            ms = [[_time(fn, ring, args.reps) for fn, ring in paths] for _ in range(args.rounds)]
+            bf, dq, tl = (sum(r[i] for r in ms) / len(ms) for i in range(3))
+            ratios = [r[1] / r[2] for r in ms]
+            tiled_rows.append(
+                f"| {name} | {inn} x {out} | {M} | {bf * 1e3:.1f} | {dq * 1e3:.1f} | "
+                f"{tl * 1e3:.1f} | {dq / tl:.2f}x | {min(ratios):.2f} .. {max(ratios):.2f} | "
+                f"{bf / tl:.2f}x |")
+            print("tiled " + tiled_rows[-1], flush=True)
         del ring_bf, ring_q
+    if tiled_rows:
+        print("\n| shape | in x out | M | bf16 F.linear us | dequant + F.linear us | tiled us | "
+              "tiled vs dequant | over the rounds | tiled vs bf16 |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        print("\n".join(tiled_rows))
     return 0
 
 
