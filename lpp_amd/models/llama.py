@@ -30,7 +30,8 @@ import torch.nn as nn
 from ..config import ModelConfig
 from ..layer_spec import LayerSpec
 from .. import ops
-from ..ops.linear import LPLinear, forward_fp8, quantize_module_fp8_, lp_linear
+from ..ops.linear import (LPLinear, forward_quantized, quantize_module_fp4_,
+                          quantize_module_fp8_, lp_linear)
 
 
 class RMSNorm(nn.Module):
@@ -516,9 +517,14 @@ class LMHeadPipe(nn.Linear):
         quantize_module_fp8_(self)
         return self
 
+    def quantize_fp4_(self) -> "LMHeadPipe":
+        """Hold the weight as MXFP4 (e2m1 + e8m0 per 32) from now on (inference only)."""
+        quantize_module_fp4_(self)
+        return self
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.weight is None:
-            return forward_fp8(self, x)
+            return forward_quantized(self, x)
         return lp_linear(x, self.weight)
 
     @staticmethod

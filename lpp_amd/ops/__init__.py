@@ -104,6 +104,7 @@ from .attention import (DocLayout, causal_attention, decode_attention,  # noqa: 
                         extend_attention_hip_supported, FP8_KV_DTYPE,
                         quantize_kv_rows_fp8)
 from .linear import quantize_weight_fp8, linear_fp8w, linear_fp8w_ref  # noqa: E402
+from .linear import quantize_weight_fp4, linear_fp4w, linear_fp4w_ref  # noqa: E402
 
 __all__ = [
     "rmsnorm",
@@ -128,6 +129,9 @@ __all__ = [
     "quantize_weight_fp8",
     "linear_fp8w",
     "linear_fp8w_ref",
+    "quantize_weight_fp4",
+    "linear_fp4w",
+    "linear_fp4w_ref",
     "extension",
     "use_hip",
     "force_eager",

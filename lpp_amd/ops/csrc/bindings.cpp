@@ -76,6 +76,8 @@ int64_t attention_extend_chunk(int64_t chunk);
 at::Tensor linear_fp8w(at::Tensor x, at::Tensor wq, at::Tensor scale);
 at::Tensor linear_fp8w_tiled(at::Tensor x, at::Tensor wq, at::Tensor scale, int64_t slices);
 at::Tensor linear_fp8w_dequant(at::Tensor wq, at::Tensor scale);
+at::Tensor linear_fp4w(at::Tensor x, at::Tensor wq, at::Tensor scale);
+at::Tensor linear_fp4w_dequant(at::Tensor wq, at::Tensor scale);
 at::Tensor mfma_test_16x16x32(at::Tensor A, at::Tensor B);
 void wgrad_f32_accum(at::Tensor x, at::Tensor dy, at::Tensor dw);
 void wgrad_f32_accum_pre(at::Tensor xT, at::Tensor dyT, at::Tensor dw);
@@ -197,6 +199,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("wq"), py::arg("scale"), py::arg("slices") = 0);
   m.def("linear_fp8w_dequant", &linear_fp8w_dequant,
         "e4m3 wq [out,in] and fp32 scale [out,in/128] -> the bf16 weight [out,in], exactly",
+        py::arg("wq"), py::arg("scale"));
+  m.def("linear_fp4w", &linear_fp4w,
+        "MXFP4 weight-only linear: bf16 x [M,in], M <= 64, times e2m1 pairs wq uint8 [out,in/2] "
+        "under e8m0 scale uint8 [out,in/32] -> bf16 y [M,out], fp32 accumulation",
+        py::arg("x"), py::arg("wq"), py::arg("scale"));
+  m.def("linear_fp4w_dequant", &linear_fp4w_dequant,
+        "e2m1 pairs wq uint8 [out,in/2] and e8m0 scale uint8 [out,in/32] -> the bf16 weight "
+        "[out,in], exactly",
         py::arg("wq"), py::arg("scale"));
   m.def("wgrad_f32_accum",&wgrad_f32_accum, "dW_f32 += dY^T @ X (hipBLASLt, beta=1)");
   m.def("wgrad_f32_accum_pre", &wgrad_f32_accum_pre,

@@ -320,6 +320,125 @@ def forward_fp8(mod: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
     return linear_fp8w(x, mod.weight_fp8, mod.weight_scale)
 
 
+# ---------------------------------------------------------------------------
+# MXFP4 weight-only linear (serving).  A weight [out, in] is held in the OCP
+# microscaling format: e2m1 nibbles, two per byte (element 2i in the low
+# nibble of byte i), and one e8m0 scale byte per (output row, block of 32
+# inputs).  code * 2^(b-127) is exact in bf16, so the product is a bf16 GEMM
+# over the dequantised weight.  Activations stay bf16 (W4A16);
+# csrc/linear_fp4w.hip.
+# ---------------------------------------------------------------------------
+FP4W_BLOCK = 32      # inputs per scale byte
+FP4W_MAX_M = 64      # rows of x the kernel serves
+FP4W_MIN_EXP = -100  # the contract on a scale byte b: |b - 127| <= 100
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """2^e as fp32 from an integer tensor, -126 <= e <= 127, on the float's bits."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def quantize_weight_fp4(w: torch.Tensor):
+    """``w [out, in]`` -> ``(wq uint8 [out, in/2], scale uint8 [out, in/32])``
+    in the MXFP4 format; needs ``in % 128 == 0`` and ``out % 16 == 0``.
+
+    Per block of 32 inputs, with amax = m 2^E, 0.5 <= m < 1: the scale is 2^e,
+    e = E - 3 if m <= 0.75 else E - 2, e >= -100, e = 0 for a block of zeros,
+    stored as the e8m0 byte e + 127.  Then 3 < amax / 2^e <= 6, nothing
+    saturates, and values round to the nearest e2m1 code, ties to the even
+    code, so |w - deq| <= amax / 4 per block.  A weight above 2^102 in
+    magnitude would need a byte above 227, outside the kernel's contract."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_fp4: weight must be [out, in], got {tuple(w.shape)}")
+    out, inn = w.shape
+    if inn % 128 or out % 16:
+        raise ValueError(f"quantize_weight_fp4: needs in % 128 == 0 and out % 16 == 0, "
+                         f"got [out, in] = [{out}, {inn}]")
+    wf = w.detach().float().view(out, inn // FP4W_BLOCK, FP4W_BLOCK)
+    bits = wf.abs().amax(-1, keepdim=True).view(torch.int32)
+    # amax = 1.f 2^(b-127) = (1.f / 2) 2^(b-126), and m <= 0.75 iff 1.f <= 1.5
+    E = (bits >> 23) - 126
+    e = torch.where((bits & 0x7FFFFF) <= 0x400000, E - 3, E - 2).clamp_(min=FP4W_MIN_EXP)
+    e = torch.where(bits == 0, torch.zeros_like(e), e)
+    v = wf.abs() * _pow2(-e)
+    # the code is the number of midpoints passed; a tie stays on the even code
+    code = ((v > 0.25).to(torch.uint8) + (v >= 0.75) + (v > 1.25) + (v >= 1.75)
+            + (v > 2.5) + (v >= 3.5) + (v > 5.0))
+    nib = (code | ((wf < 0).to(torch.uint8) << 3)).view(out, inn // 2, 2)
+    wq = nib[..., 0] | (nib[..., 1] << 4)
+    return wq.contiguous(), (e + 127).to(torch.uint8).view(out, inn // FP4W_BLOCK)
+
+
+def _dequant_weight_fp4_ref(wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The bf16 weight of (wq, scale), exactly, in stock torch ops."""
+    out, half = wq.shape
+    lut = torch.tensor(_E2M1 + tuple(-c for c in _E2M1), device=wq.device)
+    val = lut[torch.stack((wq & 15, wq >> 4), -1).long()]          # [out, in/2, 2]
+    w = val.view(out, -1, FP4W_BLOCK) * _pow2(scale.to(torch.int32) - 127)[..., None]
+    return w.view(out, 2 * half).to(torch.bfloat16)
+
+
+def linear_fp4w_ref(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``F.linear`` over the dequantised bf16 weight: the CPU path and the
+    kernel's oracle, bit for bit a model that holds the dequantised weights."""
+    return F.linear(x, _dequant_weight_fp4_ref(wq, scale).to(x.dtype))
+
+
+def linear_fp4w(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``x [..., in] @ dequant(wq, scale)^T -> [..., out]``, inference only.
+
+    ``wq`` is ``uint8 [out, in/2]``, two e2m1 values per byte, element 2i of a
+    row in the low nibble of byte i (the ``float4_e2m1fn_x2`` order); ``scale``
+    is ``uint8 [out, in/32]``, e8m0: byte b stands for 2^(b-127).  The contract
+    is 27 <= b <= 227, which keeps every dequantised value a normal bf16;
+    bytes outside it are not checked and their result is undefined.
+
+    On the GPU with bf16 x and at most 64 rows (decode ticks) the skinny
+    gfx950 kernel streams the packed weight once; its result does not depend
+    on how many rows ride together.  Above 64 rows the weight is dequantised
+    into a bf16 scratch tensor by ``linear_fp4w_dequant`` and ``F.linear``
+    (hipBLASLt) runs over it.  On the CPU or under ``LPP_FORCE_EAGER`` the op
+    is ``linear_fp4w_ref``."""
+    if not use_hip(x):
+        return linear_fp4w_ref(x, wq, scale)
+    if x.dtype is not torch.bfloat16:
+        raise ValueError(f"linear_fp4w: the gfx950 kernel takes bf16 x, got {x.dtype}")
+    ext = extension()
+    if x.dim() < 1 or wq.dim() != 2 or x.shape[-1] != 2 * wq.shape[1]:
+        raise ValueError(f"linear_fp4w: x [..., {x.shape[-1] if x.dim() else '?'}] against a "
+                         f"packed weight [out, in/2] = {tuple(wq.shape)}")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, x.shape[-1])
+    if x2.shape[0] == 0:
+        return x.new_empty(*lead, wq.shape[0])
+    if x2.shape[0] <= FP4W_MAX_M:
+        y = ext.linear_fp4w(x2, wq, scale)   # raises on a non-contiguous x
+    else:
+        y = F.linear(x2, ext.linear_fp4w_dequant(wq, scale))
+    return y.view(*lead, wq.shape[0])
+
+
+def quantize_module_fp4_(mod: torch.nn.Module) -> None:
+    """Replace ``mod.weight`` by the buffers ``weight_fp4`` / ``weight_scale``."""
+    if getattr(mod, "weight", None) is None:
+        return  # already quantised
+    wq, scale = quantize_weight_fp4(mod.weight.data)
+    mod.register_parameter("weight", None)   # the bf16 storage goes with its last reference
+    mod.register_buffer("weight_fp4", wq)
+    mod.register_buffer("weight_scale", scale)
+
+
+def forward_quantized(mod: torch.nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """The forward of a module whose weight is held quantised, by the buffer it holds."""
+    if getattr(mod, "weight_fp4", None) is None:
+        return forward_fp8(mod, x)
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{type(mod).__name__}: fp4 weights are inference-only; call under "
+                           "torch.no_grad()")
+    return linear_fp4w(x, mod.weight_fp4, mod.weight_scale)
+
+
 class LPLinear(torch.nn.Linear):
     """Drop-in nn.Linear (bias-free) using the fused-wgrad path."""
 
@@ -332,7 +451,12 @@ class LPLinear(torch.nn.Linear):
         quantize_module_fp8_(self)
         return self
 
+    def quantize_fp4_(self) -> "LPLinear":
+        """Hold the weight as MXFP4 (e2m1 + e8m0 per 32) from now on (inference only)."""
+        quantize_module_fp4_(self)
+        return self
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.weight is None:
-            return forward_fp8(self, x)
+            return forward_quantized(self, x)
         return lp_linear(x, self.weight)

@@ -87,10 +87,15 @@ class ContinuousBatchingEngine:
         decoder layers and the LM head IN PLACE (``LPLinear.quantize_fp8_``:
         e4m3 bytes and one power-of-two scale per 128 inputs of a row, half
         the weight memory); embedding and norms stay as they are.  Decode
-        ticks then run ``ops.linear_fp8w``.  Independent of ``kv_dtype`` and
+        ticks then run ``ops.linear_fp8w``.  ``torch.float4_e2m1fn_x2``
+        (opt-in) does the same in the MXFP4 format (``LPLinear.quantize_fp4_``:
+        e2m1 nibbles and one e8m0 scale byte per 32 inputs of a row, a good
+        quarter of the bf16 memory; round-to-nearest, no calibration) and
+        decode ticks run ``ops.linear_fp4w``.  Independent of ``kv_dtype`` and
         paging."""
-        if weight_dtype not in (None, torch.float8_e4m3fn):
-            raise ValueError(f"weight_dtype must be None or float8_e4m3fn, got {weight_dtype}")
+        if weight_dtype not in (None, torch.float8_e4m3fn, torch.float4_e2m1fn_x2):
+            raise ValueError("weight_dtype must be None, float8_e4m3fn or float4_e2m1fn_x2, "
+                             f"got {weight_dtype}")
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError(f"prefill_chunk must be >= 1, got {prefill_chunk}")
         if (kv_page_size is None) != (kv_pages is None):
@@ -118,7 +123,10 @@ class ContinuousBatchingEngine:
                 if isinstance(layer, (DecoderLayerPipe, LMHeadPipe)):
                     for m in layer.modules():
                         if isinstance(m, (LPLinear, LMHeadPipe)):
-                            m.quantize_fp8_()
+                            if weight_dtype is torch.float8_e4m3fn:
+                                m.quantize_fp8_()
+                            else:
+                                m.quantize_fp4_()
         self.caches = [
             RaggedKVCache(max_slots, max_seq_len, cfg.kv_heads, cfg.head_dim,
                           self.device, p.dtype, kv_dtype=kv_dtype,

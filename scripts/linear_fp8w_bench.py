@@ -1,11 +1,15 @@
 #!/usr/bin/env python
-"""Per-op timing of the FP8 weight-only linear (ops.linear_fp8w) against the
-bf16 F.linear it replaces, at the 7B and 70B projection shapes (1 GPU).
+"""Per-op timing of the FP8 and MXFP4 weight-only linears (ops.linear_fp8w,
+ops.linear_fp4w) against the bf16 F.linear they replace, at the 7B and 70B
+projection shapes (1 GPU).
 
 Each shape is timed with device events over a ring of weight copies larger
-than the last-level cache (--ring-mb), so every call streams its weight from
-HBM as a decode tick does; the two paths alternate inside one run.  TB/s counts
-the weight bytes alone (1 byte + 4/128 per element for fp8, 2 for bf16).
+than the last-level cache (--ring-mb, counted in each path's own bytes), so
+every call streams its weight from HBM as a decode tick does; the three paths
+alternate inside each of --rounds rounds.  Times are means over the rounds;
+fp4 against fp8 is given with its lowest and highest ratio over the rounds.
+TB/s counts the weight bytes alone (2 per element for bf16, 1 + 4/128 for fp8,
+1/2 + 1/32 for fp4).
 
 A second table (--tiled-ms, rows above 64) times three paths per point, in
 --rounds alternating rounds: bf16 F.linear, dequantise + F.linear (the default
@@ -67,25 +71,34 @@ def main() -> int:
     g = torch.Generator().manual_seed(0)
     shapes = [sh for sh in SHAPES if args.shapes is None or sh[0] in args.shapes]
     if args.ms:
-        print("| shape | in x out | M | bf16 F.linear us | TB/s | fp8w us | TB/s | speedup |")
-        print("|---|---|---|---|---|---|---|---|")
+        print("| shape | in x out | M | bf16 F.linear us | TB/s | fp8w us | TB/s | fp4w us | TB/s | "
+              "fp8 vs bf16 | fp4 vs bf16 | fp4 vs fp8 | over the rounds |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     tiled_rows = []
     for name, inn, out in shapes:
         w = (torch.randn(out, inn, generator=g) * 0.02).bfloat16().cuda()
         wq, sc = ops.quantize_weight_fp8(w)
-        n = max(2, -(-args.ring_mb * 2**20 // (2 * inn * out)))
-        ring_bf = [w.clone() for _ in range(n)]
-        ring_q = [(wq.clone(), sc.clone()) for _ in range(n)]
+        w4, s4 = ops.quantize_weight_fp4(w)
+        # weight bytes of one call, and a ring of copies larger than the cache for each path
+        by_bf, by_q, by_4 = 2 * inn * out, inn * out + 4 * inn * out // 128, inn * out // 2 + inn * out // 32
+        n_bf, n_q, n_4 = (max(2, -(-args.ring_mb * 2**20 // b)) for b in (by_bf, by_q, by_4))
+        ring_bf = [w.clone() for _ in range(n_bf)]
+        ring_q = [(wq.clone(), sc.clone()) for _ in range(n_q)]
+        ring_4 = [(w4.clone(), s4.clone()) for _ in range(n_4)]
         for M in args.ms:
             x = (torch.randn(M, inn, generator=g)).bfloat16().cuda()
-            ms_bf = ms_q = 0.0
-            for _ in range(2):           # the two paths alternate
-                ms_bf += _time(lambda t: F.linear(x, t), ring_bf, args.reps) / 2
-                ms_q += _time(lambda t: ops.linear_fp8w(x, *t), ring_q, args.reps) / 2
-            tb_bf = 2 * inn * out / ms_bf / 1e9
-            tb_q = (inn * out + 4 * inn * out // 128) / ms_q / 1e9
-            print(f"| {name} | {inn} x {out} | {M} | {ms_bf * 1e3:.1f} | {tb_bf:.2f} | "
-                  f"{ms_q * 1e3:.1f} | {tb_q:.2f} | {ms_bf / ms_q:.2f}x |", flush=True)
+            paths = [(lambda t: F.linear(x, t), ring_bf),
+                     (lambda t: ops.linear_fp8w(x, *t), ring_q),
+                     (lambda t: ops.linear_fp4w(x, *t), ring_4)]
+            # the three paths alternate inside a round
+            ms = [[_time(fn, ring, args.reps) for fn, ring in paths] for _ in range(args.rounds)]
+            bf, q8, q4 = (sum(r[i] for r in ms) / len(ms) for i in range(3))
+            ratios = [r[1] / r[2] for r in ms]
+            print(f"| {name} | {inn} x {out} | {M} | {bf * 1e3:.1f} | {by_bf / bf / 1e9:.2f} | "
+                  f"{q8 * 1e3:.1f} | {by_q / q8 / 1e9:.2f} | {q4 * 1e3:.1f} | {by_4 / q4 / 1e9:.2f} | "
+                  f"{bf / q8:.2f}x | {bf / q4:.2f}x | {q8 / q4:.2f}x | "
+                  f"{min(ratios):.2f} .. {max(ratios):.2f} |", flush=True)
+        del ring_4
         for M in args.tiled_ms:
             x = (torch.randn(M, inn, generator=g)).bfloat16().cuda()
             paths = [(lambda t: F.linear(x, t), ring_bf),

@@ -38,9 +38,10 @@ def main() -> int:
                          "per tick (default: whole-prompt admission)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the e4m3 KV cache (needs --prefill-chunk)")
-    ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16",
-                    help="fp8: e4m3 projection and LM-head weights (ops.linear_fp8w); the model "
-                         "is quantised in place, so the static run uses them too")
+    ap.add_argument("--weight-dtype", choices=["bf16", "fp8", "fp4"], default="bf16",
+                    help="fp8: e4m3 projection and LM-head weights (ops.linear_fp8w); fp4: MXFP4 "
+                         "ones (ops.linear_fp4w); the model is quantised in place, so the static "
+                         "run uses them too")
     args = ap.parse_args()
 
     assert torch.cuda.is_available(), "run on the GPU box"
@@ -59,8 +60,8 @@ def main() -> int:
                                    prefill_chunk=args.prefill_chunk,
                                    kv_dtype=torch.float8_e4m3fn if args.kv_dtype == "fp8"
                                    else None,
-                                   weight_dtype=torch.float8_e4m3fn
-                                   if args.weight_dtype == "fp8" else None)
+                                   weight_dtype={"bf16": None, "fp8": torch.float8_e4m3fn,
+                                                 "fp4": torch.float4_e2m1fn_x2}[args.weight_dtype])
     for i, (p, n) in enumerate(zip(prompts, lens)):
         eng.submit(Request(f"r{i}", p, n))
     finish_c = {}
